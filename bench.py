@@ -1,8 +1,20 @@
 #!/usr/bin/env python3
 """bench.py — the headline benchmark: acoustic frames/sec of full BiLSTM-CTC train steps on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, runs W warm-up and exactly K timed steps of the headline workload, and prints one JSON line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, with the HIP-event
+rooflines measured inside those steps).  Everything that needs runs of its own - the other configurations, the forward-only
+and CLI-corpus legs, the CPU oracle baseline, the CTC op at B = 512, GEMM rates from extra steps without the weight-gradient
+overlap, the whole-gradient all-reduce timed alone - runs only with `--full`.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step (rank 0): `loss.npy`, `eval_loss.npy`,
+`grad_norm.npy` (float64 scalars, as `graph.step_device` returns them) and `params.npy` / `grads.npy` (float32: the flat
+parameters after that step's update and the step's flat gradient buffer; above DUMP_MAX_ELEMS elements a fixed sample of
+positions drawn with seed DUMP_SEED, the same for every run of the same workload).  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json metric, config c4): 5 x BiLSTM-1024 (P = N, peepholes) + affine head, V = 44,
 synthetic 40-dim fbank, T = 1000, B = 64 utterances per GPU, L = 100 labels, fp32, adam lr 4e-4,
@@ -15,24 +27,24 @@ Launching: `python bench.py --gpus N` with N > 1 and no torchrun environment sta
 from --gpus, or fewer visible GPUs than ranks, is an error (non-zero exit, no JSON line) - never a smaller job under an
 N-GPU label.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (those marked [full] only with --full):
   roofline      dominant kernel (the f32 MFMA GEMM): algorithmic FLOPs / HIP-event time, measured live on the
                 launch stream over the timed steps, against the 157.3 TFLOP/s fp32 matrix peak.
   roofline_ctc  the CTC op (row stats + alpha/beta scan + gradient): algorithmic bytes T*B*(8V+8S) / time,
-                against the 8 TB/s HBM peak (north-star target: >= 40 %).
-  secondary     (c4, N = 1) the other BASELINE configs - c5, c2, c3 - and c4x3 / c2x3 / c3x3 (the fp32 configurations with
+                against the 8 TB/s HBM peak (north-star target: >= 40 %); [full] `large_batch`: the op alone at B = 512.
+  secondary     [full] (c4, N = 1) the other BASELINE configs - c5, c2, c3 - and c4x3 / c2x3 / c3x3 (the fp32 configurations with
                 their products AND recurrences as fp32-on-bf16x3 split operands, DESIGN.md sections 3f, 3g) timed in the same
                 process after the headline region (5 warm-up + 10 timed steps each): ms_per_step, frames/s, their GEMM / CTC
                 rooflines (c1 - c3: GEMM rates from three extra steps without the weight-gradient overlap).  Printed
                 compacted against the headline (`compact_secondary`; constants in `secondary_protocol`) so that the whole
                 line stays inside the driver's 8 KB window.
-  inference     (c4, N = 1) the forward pass alone on the workload's batch (is_training false): frames/s for c4, c4x3, c3
-                (the high-rank head), c3x3 and c5.
-  cli_corpus    (c4, N = 1) bin/nnet-train.py as a child process on a synthetic TFRecord corpus (c4 and c2) next to the
-                resident-input rate of the same model: what the loader + upload + run loop cost end to end.
-  allreduce     (N > 1) time the compute stream waited for gradient collectives per step, and the whole 480 MB
+  inference     [full] (c4, N = 1) the forward pass alone on the workload's batch (is_training false): frames/s for c4,
+                c4x3, c3 (the high-rank head), c3x3 and c5.
+  cli_corpus    [full] (c4, N = 1) bin/nnet-train.py as a child process on a synthetic TFRecord corpus (c4 and c2) next to
+                the resident-input rate of the same model: what the loader + upload + run loop cost end to end.
+  allreduce     (N > 1) time the compute stream waited for gradient collectives per step, and [full] the whole 480 MB
                 gradient all-reduce timed alone (algorithmic and bus bandwidth).
-  cpu_baseline  the CPU oracle (restatement of the TF-1.8 graph; TF itself is not installable) timed on this
+  cpu_baseline  [full] the CPU oracle (restatement of the TF-1.8 graph; TF itself is not installable) timed on this
                 box's host cores on a bounded sample of the same model, rank 0 at N = 1 only.
 """
 import argparse
@@ -448,7 +460,17 @@ def parse_args(argv=None):
     ap.add_argument("--host-batch", action="store_true",
                     help="hand every step the batch as HOST numpy arrays in the loader's contract (PCIe-inclusive "
                          "rate, for DESIGN.md; never the headline value)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: `secondary`, `inference`, `cli_corpus`, "
+                         "`cpu_baseline` (c4, N = 1; each still subject to its --no-* switch), the CTC op at B = 512, "
+                         "GEMM rates without the weight-gradient overlap, the whole-gradient all-reduce alone (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, eval_loss, grad_norm, parameters, gradient) "
+                         "as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -521,14 +543,43 @@ def allreduce_alone(graph, pg, device, iters=5):
             "busbw_GBs": round(2.0 * (world - 1) / world * nbytes / (ms * 1e-3) / 1e9, 1)}
 
 
+# --dump-outputs: a flat parameter / gradient vector longer than this is written as a fixed sample of this many positions
+# (16 MB of float32 each: the whole dump stays well under 64 MB); the positions depend only on the vector's length
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_SEED = 12345
+
+
+def dump_positions(n):
+    """Sorted positions of the --dump-outputs sample of a flat vector of n elements (None: the whole vector)."""
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+
+
+def dump_outputs(path, graph, out):
+    """What the timed path handed back in its last step, as float64 / float32 .npy files under `path` (module docstring)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for key in ("loss", "eval_loss", "grad_norm"):
+        np.save(os.path.join(path, key + ".npy"), np.asarray(out[key], dtype=np.float64))
+    ps = graph.model.ps
+    pos = dump_positions(ps.n)
+    idx = None if pos is None else torch.from_numpy(pos).to(ps.flat.device)
+    for key, v in (("params", ps.flat), ("grads", ps.grad)):
+        v = v.detach()[:ps.n] if idx is None else v.detach().index_select(0, idx)
+        np.save(os.path.join(path, key + ".npy"), v.to(torch.float32).cpu().numpy())
+
+
 class UnhealthyRun(RuntimeError):
     """A rank spent timed steps off the schedule the figure is quoted for (see run_workload): no value is printed."""
 
 
 def run_workload(name, steps, warmup, device, pg, rank, world, profile=True, host_batch=False, full=True,
-                 workload=None, ragged=False):
+                 workload=None, ragged=False, side_runs=True, dump_dir=None):
     """Warm-up + EXACTLY `steps` timed train steps of one workload between barrier + synchronize; returns the fields of
-    its JSON object (rank 0; other ranks get None).  full=False: the compact form used for `secondary` entries."""
+    its JSON object (rank 0; other ranks get None).  full=False: the compact form used for `secondary` entries.
+    side_runs=False: none of the measurements that need runs of their own after the timed steps (bench.py --full).
+    dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs)."""
     import torch
     from lstm_ctc_amd import ops
     from lstm_ctc_amd.nnet.graph import create_graph_for_training_ctc
@@ -601,6 +652,8 @@ def run_workload(name, steps, warmup, device, pg, rank, world, profile=True, hos
                                "; ".join("rank %d: %d fall-back(s) in the timed steps, %d in all%s" % (
                                    h["rank"], h["fallbacks_in_timed_steps"], h["persist_fallbacks"],
                                    ", latched" if h["latched"] else "") for h in sick)))
+    if dump_dir and rank == 0:           # before any untimed step below can move the parameters
+        dump_outputs(dump_dir, graph, out)
     dt, rank_ms = dt_local, None
     if pg is not None:
         gloo = torch.distributed.get_backend(pg) == "gloo"
@@ -611,13 +664,13 @@ def run_workload(name, steps, warmup, device, pg, rank, world, profile=True, hos
         dt = max(per_rank)                               # the contract: MAX over ranks
         rank_ms = {"min": round(min(per_rank) / steps * 1e3, 3), "max": round(dt / steps * 1e3, 3)}
     alone = None
-    if pg is not None and world > 1 and full:
+    if pg is not None and world > 1 and full and side_runs:
         alone = allreduce_alone(graph, pg, device)
     # c1 - c3 run their weight-gradient GEMMs on a side stream UNDER the next layer's BPTT (Model.overlap_wgrad), so a
     # GEMM's event bracket in the timed steps also holds its wait for CUs: not the kernel's rate.  Three more steps with
     # the overlap off, OUTSIDE the timed region, bracket the same launches alone: the rate the roofline object quotes.
     prof_alone = None
-    if profile and graph.model.overlap_wgrad and world == 1:
+    if profile and side_runs and graph.model.overlap_wgrad and world == 1:
         graph.model.overlap_wgrad = False
         one_step()
         ops.PROFILE = []
@@ -748,7 +801,7 @@ def run_workload(name, steps, warmup, device, pg, rank, world, profile=True, hos
                                     "avg_call_ms": round(c[1] / c[2], 4)}
             if not full:
                 line["roofline_ctc"].pop("kernel")
-            if full:
+            if full and side_runs:
                 try:        # the same op with all local micro-batches in one launch (B = 512): issue-bound regime
                     line["roofline_ctc"]["large_batch"] = ctc_large_batch(w, device)
                 except Exception as exc:
@@ -924,7 +977,8 @@ def main(argv=None):
 
     try:
         res = run_workload(args.workload, args.steps, args.warmup, device, pg, rank, world,
-                           profile=not args.no_profile, host_batch=args.host_batch)
+                           profile=not args.no_profile, host_batch=args.host_batch, side_runs=args.full,
+                           dump_dir=args.dump_outputs)
     except UnhealthyRun as exc:           # every rank raises it (the verdict is all-gathered): no JSON line, non-zero
         if rank == 0:
             sys.stderr.write("bench.py: %s; refusing to print a value\n" % exc)
@@ -946,7 +1000,7 @@ def main(argv=None):
                                         "torch.distributed.run" if pg is not None else "bare python")
         line.update(res)
     # the other BASELINE configs in front of the same clock: after the headline's timed region, same process, N = 1
-    if world == 1 and args.workload == "c4" and not args.no_secondary:
+    if args.full and world == 1 and args.workload == "c4" and not args.no_secondary:
         sec = {}
         for name in SECONDARY_DEFAULT:
             try:
@@ -963,7 +1017,7 @@ def main(argv=None):
         if rank == 0:
             line["secondary"] = sec
     # the product's real entry point on a TFRecord corpus, next to the resident-input rate of the same model
-    if world == 1 and args.workload == "c4" and not args.no_cli_corpus:
+    if args.full and world == 1 and args.workload == "c4" and not args.no_cli_corpus:
         line["cli_corpus"] = {}
         for name in ("c4", "c2"):
             try:
@@ -971,7 +1025,7 @@ def main(argv=None):
             except Exception as exc:
                 line["cli_corpus"][name] = {"error": repr(exc)}
     # the forward pass alone (what nnet-forward runs per batch of utterances), fp32 and split-operand
-    if world == 1 and args.workload == "c4" and not args.no_secondary:
+    if args.full and world == 1 and args.workload == "c4" and not args.no_secondary:
         line["inference"] = {}
         for name in ("c4", "c4x3", "c3", "c5"):
             try:
@@ -979,7 +1033,7 @@ def main(argv=None):
             except Exception as exc:
                 line["inference"][name] = {"error": repr(exc)}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 if args.workload in CPU_FULL_NEED_GB and not args.host_batch:
                     # the WHOLE benched batch once (c4: ~75 s on 16 cores), after every GPU leg; the bounded sample of

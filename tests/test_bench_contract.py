@@ -161,3 +161,29 @@ def test_the_committed_round6_line():
     assert 0.15 < rg["ragged"]["padded_frame_share"] < 0.25 and rg["value"] < line["value"]
     assert abs(rg["ragged"]["padded_frames_s"] / line["value"] - 1.0) < 0.03      # a ragged step costs what the padded one costs
     assert b.finalize_line(line) == line                                        # what main() printed is already compact
+
+
+def test_plain_run_options():
+    """A plain run takes no side measurements (`--full` is off by default), `--steps` is the timed step count and must
+    be at least one, and `--dump-outputs DIR` names the directory the last timed step's arrays go to."""
+    import pytest
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = b.parse_args(["--steps", "3", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            b.parse_args(bad)
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs writes a flat vector whole up to DUMP_MAX_ELEMS elements, else the same seeded sample of positions
+    on every run: the c4 dump (parameters + gradient, float32, ~120 M elements each) stays inside 64 MB."""
+    b = _bench()
+    assert b.dump_positions(1000) is None and b.dump_positions(b.DUMP_MAX_ELEMS) is None
+    n = 120_000_000
+    p, q = b.dump_positions(n), b.dump_positions(n)
+    assert p.dtype.kind == "i" and (p == q).all() and len(p) <= b.DUMP_MAX_ELEMS
+    assert (p[1:] > p[:-1]).all() and p[0] >= 0 and p[-1] < n
+    assert 2 * 4 * b.DUMP_MAX_ELEMS + 3 * 1024 <= 64 << 20

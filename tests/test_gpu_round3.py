@@ -112,7 +112,8 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     for buckets in ("1", "0"):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-               "--workload", "c4" if buckets == "1" else "c2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+               "--workload", "c4" if buckets == "1" else "c2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+               "--full"]
         r = subprocess.run(cmd, capture_output=True, timeout=1200, env=dict(env, LC_DP_BUCKETS=buckets), cwd=ROOT)
         assert r.returncode == 0, r.stderr.decode()[-3000:]
         lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]

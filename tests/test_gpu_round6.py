@@ -77,7 +77,7 @@ def test_bench_eight_ranks_rehearsal(tmp_path, name, buckets, overlap):
     env = _clean_env(LC_BENCH_SHARED_GPU="1", LC_LSTM_PERSISTENT="0", LC_DP_BUCKETS=buckets, LC_OVERLAP_WGRAD=overlap,
                      LC_BENCH_DUMP_DIR=str(dump))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--workload", name,
-           "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline"]
+           "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-4000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]

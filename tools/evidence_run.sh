@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end evidence on the GPU box (development only): the full GPU test suite, the default bench line (headline c4 +
+# Round-end evidence on the GPU box (development only): the full GPU test suite, the --full bench line (headline c4 +
 # secondary c5 / c4x3 / c2 / c3 + the bin/nnet-train.py corpus leg) and one line per BASELINE config, the rocprofv3 kernel
 # statistics of the same commands, the PMC traffic passes, and the probes DESIGN.md quotes.
 #   gpurun --timeout 3300 -- 'bash tools/evidence_run.sh <tag> [round-prefix]'      -> gpurun_out/<tag>/
@@ -12,11 +12,11 @@ if [ -z "$SKIP_TESTS" ]; then
     timeout 1800 python -m pytest tests -m gpu -x -q > $out/${r}_pytest_gpu.log 2>&1; tail -3 $out/${r}_pytest_gpu.log
 fi
 t0=$(date +%s)
-timeout 900 python bench.py > $out/${r}_bench_default.json 2> $out/default.err
+timeout 900 python bench.py --full > $out/${r}_bench_default.json 2> $out/default.err
 echo "default bench.py run: $(( $(date +%s) - t0 )) s wall" > $out/${r}_bench_default_wall.txt
 cut -c1-200 $out/${r}_bench_default.json
 for w in c1 c2 c3 c5 c4x3 c3x3 c2x3; do
-    timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $out/${r}_bench_$w.json 2> $out/$w.err
+    timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --full > $out/${r}_bench_$w.json 2> $out/$w.err
     cut -c1-160 $out/${r}_bench_$w.json
 done
 for w in c2 c3 c4 c5 c4x3 c3x3 c2x3; do

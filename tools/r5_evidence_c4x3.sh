@@ -6,11 +6,11 @@ tag=${1:-r5ev3}; r=r5; out=gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 cp profiles/r5_pmc_traffic.json $out/${r}_pmc_traffic.json
 t0=$(date +%s)
-timeout 900 python bench.py > $out/${r}_bench_default.json 2> $out/default.err
+timeout 900 python bench.py --full > $out/${r}_bench_default.json 2> $out/default.err
 echo "default bench.py run: $(( $(date +%s) - t0 )) s wall" > $out/${r}_bench_default_wall.txt
 cut -c1-200 $out/${r}_bench_default.json
 w=${W:-c4x3}
-timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $out/${r}_bench_$w.json 2> $out/$w.err
+timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --full > $out/${r}_bench_$w.json 2> $out/$w.err
 rm -rf $out/prof_$w
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$w -o p -- python3 bench.py --workload $w --steps 8 --warmup 2 --no-cpu-baseline --no-profile --no-secondary --no-cli-corpus > $out/prof_$w.json 2> $out/prof_$w.err
 f=$(find $out/prof_$w -name "*kernel_stats.csv" | head -1)

@@ -7,11 +7,11 @@ out=gpurun_out/r6ev
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 t0=$(date +%s)
-timeout 900 python bench.py > $out/${r}_bench_default.json 2> $out/default.err
+timeout 900 python bench.py --full > $out/${r}_bench_default.json 2> $out/default.err
 echo "default bench.py run: $(( $(date +%s) - t0 )) s wall" > $out/${r}_bench_default_wall.txt
 tail -c 1200 $out/${r}_bench_default.json; cat $out/${r}_bench_default_wall.txt
 for w in c1 c2 c3 c5 c4x3; do
-    timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $out/${r}_bench_$w.json 2> $out/$w.err
+    timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --full > $out/${r}_bench_$w.json 2> $out/$w.err
     cut -c1-160 $out/${r}_bench_$w.json
 done
 for w in c2 c3 c4 c5; do

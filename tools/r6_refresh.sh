@@ -3,7 +3,7 @@
 out=gpurun_out/r6ev2; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 for w in c5; do
-    timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $out/r6_bench_$w.json 2> $out/$w.err
+    timeout 600 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --full > $out/r6_bench_$w.json 2> $out/$w.err
     cut -c1-160 $out/r6_bench_$w.json
 done
 for w in c4 c5; do
