@@ -379,6 +379,17 @@ int lc_bn_update_moving(float *moving_mean, float *moving_var, const float *mean
  * longer zero (a ResidualWrapper input that went through batch normalisation): x[t*B+b, :] = 0 for t >= seq_len[b]. */
 int lc_length_mask(float *x, int T, int B, int C, int ldx, const int *seq_len, lc_stream_t stream);
 
+/* ------------------------------------------------------------------ packed frames ----------- */
+/* A ragged batch's live frames as a dense matrix (nnet/frames.py: FrameMap; no reference counterpart): the products that
+ * read a layer's INPUT run on `Mp` packed rows instead of T * B padded ones.  Row maps are device int32, -1 = no source row.
+ *   lc_pack_rows    out[r, :] = rows[r]    >= 0 ? x[rows[r], :]    : 0   for r < Mp           (padded -> packed)
+ *   lc_unpack_rows  out[q, :] = inverse[q] >= 0 ? x[inverse[q], :] : 0   for q < rows = T * B (packed -> padded)
+ * Every output row is written exactly once (no memset needed, deterministic); zero rows are +0.0.  ldx / ldo: row pitches in
+ * floats (column windows of wider buffers are fine).  C % 4 == 0 with 16-byte aligned rows takes 16-byte accesses, anything
+ * else a scalar path.  A map entry must name a row of x: the caller's contract, nothing here can check it. */
+int lc_pack_rows(const float *x, int ldx, const int *rows, int Mp, int C, float *out, int ldo, lc_stream_t stream);
+int lc_unpack_rows(const float *x, int ldx, const int *inverse, int rows, int C, float *out, int ldo, lc_stream_t stream);
+
 /* ------------------------------------------------------------------ development hook -------- */
 /* Not part of the product surface: when set to a device buffer of [T][4 waves][8] 64-bit words, one workgroup of
  * the forward step kernel stores s_memtime stamps of its phases there (tools/stamp_probe.py); NULL switches it off. */

@@ -252,21 +252,22 @@ class CTCGraph:
         x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = up
         self._validate_labels(flat)
         out = self.step_device(x, seq_d, flat_d, offs_d, maxlen, int(len(flat)), fetch_eval=fetch_eval,
-                               fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs)
+                               fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs, seq_host=seq)
         out["sequence_length"] = seq
         return out
 
     def step_device(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval=False, fetch_logits=False, train=None,
-                    flat_host=None, offs_host=None):
+                    flat_host=None, offs_host=None, seq_host=None):
         """The same step on tensors already resident in HBM: x [T,B,D] time-major f32, seq_d [B] i32,
-        labels flat i32 + offsets [B+1] i32.
+        labels flat i32 + offsets [B+1] i32.  seq_host: seq_d's values on the host, when the caller has them (pack_frames
+        then builds a new batch's frame map without a device-to-host copy).
 
         A persistent-recurrence launch that cannot complete (lstm_ctc_hip.h: bounded waits, sticky status word) leaves
         NaN outputs and makes the optimizer skip its update on the device; the word is read at the step's one sync
         point and the step is then re-run, in this process, with the per-step launch train."""
         train = self.training if train is None else train
         counters = (self.global_step, self.drop_seed, self.opt_step)
-        args = (x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host)
+        args = (x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host, seq_host)
         if self._fallback.latched:                     # co-residency is structurally unavailable: stay on the train
             with ops.force_launch_train():
                 out, status = self._step_once(*args)
@@ -286,12 +287,13 @@ class CTCGraph:
             raise RuntimeError("LSTM recurrence failed on the launch train as well (status %d)" % status)
         return out
 
-    def _step_once(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host):
+    def _step_once(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
+                   seq_host=None):
         dev = self.model.device
         ops.lstm_status(dev).zero_()
         self.global_step += 1
         self.drop_seed = (self.drop_seed * 1664525 + 1013904223) & 0x7FFFFFFF
-        logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed)          # [T,B,V]
+        logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed, seq_len_host=seq_host)      # [T,B,V]
         loss_b, grad = ops.ctc_loss(logits, flat_d, offs_d, seq_d, maxlen, want_grad=train)
         out = {"size": size}
         tokens = out_len = None

@@ -226,6 +226,8 @@ def x3_forward_recurrence(N):
     return N > X3_FWD_MIN_N
 
 
+_PACK_FALLBACK_LOGGED = False      # "pack_frames needs fp32" is said once per process
+
 X3_FORCE = False          # tests: every eligible product on the bf16x3 kernels, whatever its size
 X3_MIN_FILL = int(os.environ.get("LC_X3_MIN_FILL", "45"))     # per cent of whole 256-CU rounds (development knob)
 
@@ -314,6 +316,41 @@ class Model:
         # DropoutWrapper masks (and the bf16 shadows of what they produce) ride in the epilogue of the product that
         # writes the masked matrix (lc_gemm_next_epilogue); LC_FUSE_DROPOUT=0 -> separate lc_dropout_scale passes
         self.fuse_dropout = os.environ.get("LC_FUSE_DROPOUT", "1") != "0"
+        # Extension key pack_frames (default off; LC_PACK_FRAMES=1|0 overrides the config): on a ragged batch the products that
+        # read a layer's input - zx, dKx, dX - run on a packed copy of the live frames (lc_pack_rows / lc_unpack_rows, DESIGN.md
+        # section 2); recurrences, projection, head, CTC stay on the padded rows.  fp32 only: the bf16 modes read their operands
+        # through shadows (bf16: shadow-ONLY activations) that have no packed form yet - they log one line and run padded.
+        pf = os.environ.get("LC_PACK_FRAMES")
+        self.pack_frames = bool(self.cfg.get("pack_frames") or False) if pf is None else pf != "0"
+        if self.pack_frames and (self.bf16 or self.x3):
+            global _PACK_FALLBACK_LOGGED
+            if not _PACK_FALLBACK_LOGGED:
+                _PACK_FALLBACK_LOGGED = True
+                from . import tflog
+                tflog.info("pack_frames is built for compute_dtype = fp32 only; compute_dtype = %s runs on the padded rows" % cd)
+            self.pack_frames = False
+        self.packed = False          # what the last forward() did: True = the input products ran on packed frames
+        self._frame_map = None       # (key, the lengths the key was made from, FrameMap) of the last ragged batch
+
+    def frame_map(self, seq_len, T, B, seq_len_host=None):
+        """The FrameMap of this batch, built once per distinct batch.  With ``seq_len_host`` (the lengths as a host array: a
+        caller that has them, CTCGraph.step, passes them and no synchronisation happens) the last map is re-used while the
+        array compares equal.  Without it the key is the device tensor's identity and state, (data_ptr, _version, T, B): a loop
+        that re-uses one tensor (step_device, bench.py) pays the device-to-host copy once, an in-place change of the lengths
+        bumps _version, and the entry keeps the tensor alive so that its address cannot be handed to another one."""
+        from .frames import FrameMap
+        hit = self._frame_map
+        if seq_len_host is not None:
+            host = np.ascontiguousarray(seq_len_host, dtype=np.int32)
+            if hit is not None and hit[0] == ("host", T, B) and np.array_equal(hit[1], host):
+                return hit[2]
+            self._frame_map = (("host", T, B), host.copy(), FrameMap(host, T, B))
+        else:
+            key = (seq_len.data_ptr(), seq_len._version, T, B)
+            if hit is not None and hit[0] == key:
+                return hit[2]
+            self._frame_map = (key, seq_len, FrameMap(seq_len.cpu().numpy(), T, B))
+        return self._frame_map[2]
 
     # ---- products with an activation operand: follow compute_dtype (weight-only products stay ops.gemm / fp32)
     def _shadow(self, t, tr):
@@ -433,14 +470,21 @@ class Model:
         return ["drnn%d/lstm_cell" % i]
 
     # ------------------------------------------------------------------------------------ forward
-    def forward(self, x, seq_len, drop_seed=0):
-        """x [T,B,D] f32 cuda, seq_len [B] int32 cuda -> logits [T,B,V] (time-major)."""
+    def forward(self, x, seq_len, drop_seed=0, seq_len_host=None):
+        """x [T,B,D] f32 cuda, seq_len [B] int32 cuda -> logits [T,B,V] (time-major).  seq_len_host: the same lengths as a
+        host array, if the caller has them (pack_frames then needs no device-to-host copy for a new batch)."""
         ps = self.ps
         self._shadows.clear()                       # parameters moved since the last step; activations are new
         T, B, D = x.shape
         assert D == ps.D, (D, ps.D)
         rows, N, P = T * B, ps.N, ps.Pout
         dev = x.device
+        # pack_frames: a batch with dead frames runs its input products on the M live rows (rounded up to Mp); one without
+        # (M == T * B; or with no live frame at all) takes the padded path untouched.  The test is M, not Mp: at a few frames
+        # Mp, a multiple of 256, can exceed T * B and the packed path is still the one asked for.
+        fm = self.frame_map(seq_len, T, B, seq_len_host) if self.pack_frames else None
+        self.packed = fm is not None and 0 < fm.M < rows
+        pk_rows, pk_inverse = fm.device(dev) if self.packed else (None, None)
         inp = x.reshape(rows, D)
         bn_saved = {}
 
@@ -461,8 +505,13 @@ class Model:
             # (the two directions' zx products on two streams - so that one's first round of tiles fills the other's partial
             # last one - measured in round 6 at c4: 338.7 / 338.7 against 340.9 / 338.7 ms; not taken, like round 4's attempt
             # with the weight gradients)
+            inp_packed = ops.pack_rows(inp, pk_rows) if self.packed else None       # [Mp, I]: live frames, zero tail rows
             for d, c in enumerate(cells):
-                zx = self._mm(inp, c["Kx"], bias=c["bias"])                          # hoisted x_t.Kx + b
+                if self.packed:
+                    # live rows only; the dead rows of zx are zero instead of the bias: the recurrences select them away
+                    zx = ops.unpack_rows(self._mm(inp_packed, c["Kx"], bias=c["bias"]), pk_inverse)
+                else:
+                    zx = self._mm(inp, c["Kx"], bias=c["bias"])                      # hoisted x_t.Kx + b
                 R = ops.gemm(c["proj"], c["Kh"]) if c["proj"] is not None else c["Kh"]
                 cs = torch.empty((rows, N), dtype=torch.float32, device=dev)
                 hs = torch.empty((rows, N), dtype=torch.float32, device=dev)
@@ -526,7 +575,7 @@ class Model:
                         ops.length_mask_(Y, seq_len, T, B)    # dynamic_rnn zeroes the wrapped cell's output there
                 if self.keep < 1.0:
                     ops.dropout_scale(Y, self.keep, drop_seed, 2 * i)
-            layers.append(dict(inp=inp, dirs=dirs, cells=cells, Y=Y, residual=residual))
+            layers.append(dict(inp=inp, inp_packed=inp_packed, dirs=dirs, cells=cells, Y=Y, residual=residual))
             inp = batch_norm("drnn_bn%d" % i, Y) if ps.use_bn else Y                  # lstm.py:288-294
         head = {}
         if ps.E > 0:
@@ -537,7 +586,7 @@ class Model:
         else:
             logits = self._mm(inp, ps.p("Variable"), bias=ps.p("Variable_1"))
         self.saved = dict(layers=layers, head=head, T=T, B=B, seq_len=seq_len, drop_seed=drop_seed, bn=bn_saved,
-                          top=inp)
+                          top=inp, frames=(pk_rows, pk_inverse) if self.packed else None)
         return logits.view(T, B, ps.V)
 
     def encoder(self):
@@ -582,6 +631,8 @@ class Model:
         ps.grad.zero_()
         top = sv["top"]
         keepalive = []
+        packed = sv["frames"] is not None
+        pk_rows, pk_inverse = sv["frames"] if packed else (None, None)
 
         def batch_norm_bwd(name, d):
             b = sv["bn"][name]
@@ -593,8 +644,8 @@ class Model:
             """The epilogue that finishes layer i's dY inside the product writing it (the DropoutWrapper's backward: the
             forward mask again, per direction), plus the bf16 shadow both products of each half (dh, dproj) read -
             or (None, None) when layer i masks in a pass of its own."""
-            if not (self.fuse_dropout and ps.blstm and self.keep < 1.0 and not ps.use_bn):
-                return None, None
+            if not (self.fuse_dropout and ps.blstm and self.keep < 1.0 and not ps.use_bn) or packed:
+                return None, None          # (packed: the mask hashes the PADDED row index - it goes on the unpacked dY below)
             d16 = (torch.empty((rows, width), dtype=torch.bfloat16, device=dl.device)
                    if self.bf16 and self.use_shadows and P % 4 == 0 else None)
             # (shadow_only: dY is read through the shadow by both products of each half - dh = half . proj^T, dproj = hs^T half)
@@ -686,7 +737,16 @@ class Model:
                 if bd.get("dz_x3") is not None:
                     t_ = bd["gates"]
                     self._shadows[(t_.data_ptr(), tuple(t_.shape), t_.stride(0), False, "x3")] = (t_, bd["dz_x3"])
-            dinp = torch.empty((rows, inp.shape[1]), dtype=torch.float32, device=dY.device) if need_dinp else None
+            # packed frames: dz's live rows, once per direction, for dKx and dX; dX is formed on packed rows and unpacked into
+            # the padded dinp (dead rows zero - what dz = 0 there gives the padded product).  Packed on the main stream, in
+            # front of the event the side stream waits for.
+            dzp = [ops.pack_rows(bd["gates"], pk_rows) for bd in bdirs] if packed else None
+            xin, dzs_in = (L["inp_packed"], dzp) if packed else (inp, [bd["gates"] for bd in bdirs])
+            dinp = None
+            if need_dinp and not packed:
+                dinp = torch.empty((rows, inp.shape[1]), dtype=torch.float32, device=dY.device)
+            # the buffer the dX products write: dinp itself, or its packed form
+            dxo = torch.empty((pk_rows.shape[0], inp.shape[1]), dtype=torch.float32, device=dY.device) if need_dinp and packed else dinp
             ep, next16 = masked_dY(i - 1, inp.shape[1]) if i > 0 else (None, None)    # rides on the LAST product into dinp
             overlap = self.overlap_wgrad and i > 0
             side_x3 = not (overlap and self.x3_side_f32)
@@ -696,14 +756,16 @@ class Model:
                        and self.fuse_dx)
             # ... and the same in float32 (lc_gemm_f32_nt2; not in bf16x3 mode, whose products are split-operand ones)
             fuse_dx32 = (not self.bf16 and not self.x3 and ndir == 2 and need_dinp and not overlap and self.fuse_dx
-                         and bdirs[0]["gates"].stride(0) == bdirs[1]["gates"].stride(0)
+                         and dzs_in[0].stride(0) == dzs_in[1].stride(0)
                          and cells[0]["Kx"].stride(0) == cells[1]["Kx"].stride(0))
             if overlap and need_dinp:            # the next layer's BPTT waits for this only: issue it first
                 # (the two-segment product here too was measured in round 6: c3 80.8 / 81.5 -> 80.7 / 81.5 ms, c2 inside its
                 # run-to-run spread - not taken)
                 for d, c in enumerate(cells):
-                    self._mm(bdirs[d]["gates"], c["Kx"], tb=True, out=dinp, beta=(0.0 if d == 0 else 1.0),
+                    self._mm(dzs_in[d], c["Kx"], tb=True, out=dxo, beta=(0.0 if d == 0 else 1.0),
                              epilogue=ep if d == ndir - 1 else None)
+                if packed:
+                    dinp = ops.unpack_rows(dxo, pk_inverse)
             main = torch.cuda.current_stream()
             if overlap:
                 if self._side is None:
@@ -711,14 +773,14 @@ class Model:
                 ev = torch.cuda.Event()
                 ev.record(main)
                 self._side.wait_event(ev)
-                keepalive.append((dY, bdirs))    # read on the side stream after main has dropped its references
+                keepalive.append((dY, bdirs, dzp))    # read on the side stream after main has dropped its references
             with torch.cuda.stream(self._side if overlap else main):
                 for d, c in enumerate(cells):
                     pre = c["prefix"]
                     dz, hs = bdirs[d]["gates"], dirs[d]["hs"]
                     gk = ps.g(pre + "/kernel")
                     I = c["I"]
-                    self._mm(inp, dz, ta=True, out=gk[:I], x3_ok=side_x3)                    # dKx = X^T dZ
+                    self._mm(xin, dzs_in[d], ta=True, out=gk[:I], x3_ok=side_x3)             # dKx = X^T dZ
                     if T > 1:                                                                # dR = M'_{prev}^T dZ
                         if dirs[d]["reverse"]:
                             hprev, dzs = hs[B:], dz[:rows - B]
@@ -762,10 +824,12 @@ class Model:
                         if T > 1:
                             ops.gemm(dR, c["Kh"], tb=True, out=gp, beta=1.0)                 # from R = proj.Kh
                     if need_dinp and not overlap and not fuse_dx and not fuse_dx32:
-                        self._mm(dz, c["Kx"], tb=True, out=dinp, beta=(0.0 if d == 0 else 1.0),
+                        self._mm(dzs_in[d], c["Kx"], tb=True, out=dxo, beta=(0.0 if d == 0 else 1.0),
                                  epilogue=ep if d == ndir - 1 else None)
                 if fuse_dx32:
-                    ops.gemm_nt2(bdirs[0]["gates"], cells[0]["Kx"], bdirs[1]["gates"], cells[1]["Kx"], out=dinp, epilogue=ep)
+                    ops.gemm_nt2(dzs_in[0], cells[0]["Kx"], dzs_in[1], cells[1]["Kx"], out=dxo, epilogue=ep)
+                if packed and need_dinp and not overlap:
+                    dinp = ops.unpack_rows(dxo, pk_inverse)
                 if fuse_dx:
                     ops.gemm_bf16_nt2(self._shadow(bdirs[0]["gates"], tr=False), self._shadow(cells[0]["Kx"], tr=False),
                                       self._shadow(bdirs[1]["gates"], tr=False), self._shadow(cells[1]["Kx"], tr=False),

@@ -481,6 +481,36 @@ def length_mask_(x, seq_len, T, B):
     return x
 
 
+# ------------------------------------------------------------------------------------------ packed frames
+def _gather_rows(fn, x, index, out):
+    lib = _lib.load()
+    _require_cuda(x, index, out)
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
+    assert index.dim() == 1 and index.dtype == torch.int32 and index.is_contiguous()
+    n, C = index.shape[0], x.shape[1]
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float32, device=x.device)
+    assert out.dim() == 2 and out.shape == (n, C) and out.dtype == torch.float32 and out.stride(1) == 1
+    ldx = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), C)
+    ldo = out.stride(0) if n > 1 else max(out.stride(0), C)
+    ev = _prof_begin()
+    _lib.check(getattr(lib, fn)(_ptr(x), ldx, _ptr(index), n, C, _ptr(out), ldo, _stream()), fn)
+    _prof_end("pack", 8.0 * n * C, ev)           # bytes moved when every row has a source: 4 read + 4 written
+    return out
+
+
+def pack_rows(x, rows, out=None):
+    """out[r, :] = x[rows[r], :] where rows[r] >= 0, else +0: the live frames of the time-major x [T*B, C] (a 2-D view, last
+    stride 1) as a dense [Mp, C] matrix.  rows: device int32 [Mp], nnet.frames.FrameMap.rows - every entry < x.shape[0]."""
+    return _gather_rows("lc_pack_rows", x, rows, out)
+
+
+def unpack_rows(x, inverse, out=None):
+    """out[q, :] = x[inverse[q], :] where inverse[q] >= 0, else +0: the packed x [Mp, C] back on the T*B padded rows, dead
+    rows zero.  inverse: device int32 [T*B], FrameMap.inverse - every entry < x.shape[0]."""
+    return _gather_rows("lc_unpack_rows", x, inverse, out)
+
+
 # ------------------------------------------------------------------------------------------ bf16 shadow operands (c5)
 def cast_bf16(x, nat=True, tr=False, out_nat=None):
     """bf16 copies of the float32 matrix x [rows, C]: (nat [rows, C] or None, tr [C, rows8] or None), rows8 = rows
