@@ -363,7 +363,9 @@ int lc_posteriors(const float *logits, int rows, int V, float smooth, int apply_
  *   lc_bn_apply          normalise with the given mean / var (batch moments, or the moving averages at inference)
  *   lc_bn_bwd            dx, dgamma, dbeta (overwritten); training != 0: gradient through the batch moments
  *   lc_bn_update_moving  assign_moving_average, v -= (v - batch) * (1 - momentum), the UPDATE_OPS of
- *                        nnet/graph.py:194-196 (momentum = 0.99)
+ *                        nnet/graph.py:194-196 (momentum = 0.99).  TensorFlow's arithmetic bit for bit: the decay is
+ *                        1 - momentum taken in double and THEN rounded to float (0.01f; 1.0f - 0.99f is 0.00999999f), the
+ *                        product and the difference are rounded separately
  * dx may alias dy. */
 size_t lc_bn_workspace_bytes(int C);
 int lc_bn_moments(const float *x, int rows, int C, int ldx, float *mean, float *var, void *workspace,
@@ -374,7 +376,7 @@ int lc_bn_bwd(const float *x, const float *dy, int rows, int C, int ldx, int ldd
               const float *var, const float *gamma, float eps, int training, float *dx, int lddx,
               float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, lc_stream_t stream);
 int lc_bn_update_moving(float *moving_mean, float *moving_var, const float *mean, const float *var, int C,
-                        float momentum, lc_stream_t stream);
+                        double momentum, lc_stream_t stream);
 /* dynamic_rnn's zero output beyond sequence_length, re-applied to a time-major x[T*B, C] whose padded rows are no
  * longer zero (a ResidualWrapper input that went through batch normalisation): x[t*B+b, :] = 0 for t >= seq_len[b]. */
 int lc_length_mask(float *x, int T, int B, int C, int ldx, const int *seq_len, lc_stream_t stream);

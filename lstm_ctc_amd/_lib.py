@@ -34,7 +34,7 @@ SIGNATURES = {
                             c_int, c_void_p]),
     "lc_bn_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_int,
                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "lc_bn_update_moving": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    "lc_bn_update_moving": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p]),
     "lc_cast_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "lc_gemm_bf16_nt": (c_int, [c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int,
                                 c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -130,11 +130,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restri
     }
 }
 
-// assign_moving_average: v -= (v - value) * (1 - momentum)
+// assign_moving_average: v -= (v - value) * (1 - momentum), as two TensorFlow ops: the product is rounded before the
+// difference (no fma), and the decay is float(1 - momentum) of the double momentum
 __global__ __launch_bounds__(256) void bn_moving_kernel(float *__restrict__ mm, float *__restrict__ mv,
                                                         const float *__restrict__ mean, const float *__restrict__ var,
                                                         int C, float one_minus_momentum)
 {
+#pragma clang fp contract(off)
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     mm[c] -= (mm[c] - mean[c]) * one_minus_momentum;
@@ -223,12 +225,12 @@ extern "C" int lc_bn_bwd(const float *x, const float *dy, int rows, int C, int l
 }
 
 extern "C" int lc_bn_update_moving(float *moving_mean, float *moving_var, const float *mean, const float *var, int C,
-                                   float momentum, lc_stream_t stream)
+                                   double momentum, lc_stream_t stream)
 {
-    LC_CHECK_ARG(moving_mean && moving_var && mean && var && C > 0 && momentum >= 0.f && momentum <= 1.f,
+    LC_CHECK_ARG(moving_mean && moving_var && mean && var && C > 0 && momentum >= 0.0 && momentum <= 1.0,
                  "lc_bn_update_moving: bad argument");
     hipLaunchKernelGGL(bn_moving_kernel, dim3(lc_cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, moving_mean,
-                       moving_var, mean, var, C, 1.0f - momentum);
+                       moving_var, mean, var, C, (float)(1.0 - momentum));
     LC_CHECK_LAUNCH("bn_update_moving");
     return LC_OK;
 }
