@@ -65,6 +65,7 @@ POSITIONAL = {
     'nnet_in': ('<nnet-in>', 'checkpoint to start from (safetensors at exactly this path)'),
     'nnet_out': ('<nnet-out>', 'checkpoint to write (safetensors at exactly this path)'),
     'nnet_output': ('<nnet-output-wspecifier>', 'Kaldi table wspecifier (ark:... / ark,t:... / ark,scp:...) for the outputs'),
+    'alignment': ('<alignment-wspecifier>', 'Kaldi int32-vector table wspecifier for the per-frame symbols (new: nnet-align)'),
 }
 FLAGS = {
     '--objective': dict(type=str, default='xent', help='training criterion; only "ctc" is implemented (the recipes pass it)'),
@@ -83,6 +84,8 @@ FLAGS = {
     '--class-prior': dict(type=str, default=None, help='label.counts file; its log-prior is subtracted from the log-posteriors'),
     '--smooth-factor': dict(type=float, default=1.0, help='temperature multiplied into the logits before the softmax'),
     '--batch-utts': dict(type=int, default=16, help='utterances per padded GPU batch (new; results do not depend on it)'),
+    '--segments': dict(type=str, default=None, help='also write text lines "key label start_frame num_frames" here (new: nnet-align)'),
+    '--scores': dict(type=str, default=None, help='also write text lines "key best_path_log_prob" here (new: nnet-align)'),
 }
 
 

@@ -66,6 +66,26 @@ int lc_ctc_loss(const float *logits, int T, int B, int V, const int *labels,
 int lc_ctc_greedy(const float *logits, int T, int B, int V, const int *seq_len, int *tokens,
                   int *out_len, int *argmax_workspace, lc_stream_t stream);
 
+/* CTC forced alignment: the best (Viterbi) path through the same 2L+1 lattice lc_ctc_loss sums over.  No reference
+ * counterpart (TF 1.8 has no such op).  Conventions of lc_ctc_loss: logits [T,B,V] time-major fp32, labels flat int32 +
+ * label_offsets [B+1], blank = V-1, ctc_merge_repeated transitions (stay, s-1, and s-2 only onto a non-blank that differs
+ * from the label two positions back); the path starts in position 0 or 1 and ends in S-1 or S-2 (S = 2L+1).
+ *   ali [B,T]          symbol per frame (blank = V-1); -1 for t >= seq_len[b] and for utterances without a path;
+ *   label_index [B,T]  index into utterance b's label sequence; -1 on blank frames and wherever ali is -1; may be NULL;
+ *   score [B]          max over paths of sum_t log_softmax(logits[t,b,:])[path_t], natural log; -inf without a path
+ *                      (more labels than frames, or too few frames for the blanks between repeated labels - not an
+ *                      error); 0 for seq_len 0.  L = 0 gives the all-blank path.
+ * Every element of ali, label_index and score is written on every call (no memset needed); the result is deterministic
+ * and bit-identical from call to call.  Arithmetic: a cell's emission is the fp32 log-softmax (fp32 log-sum-exp per frame);
+ * the sums along paths are carried in double.  Tie rule (exact comparisons): at a cell stay is preferred over s-1 over
+ * s-2; at the end S-1 over S-2.  Shapes: whatever lc_ctc_loss accepts (T, B > 0, V >= 2, 0 <= max_label_len <= 1023);
+ * anything else is LC_EINVAL with no launch, a workspace below lc_ctc_align_workspace_bytes is LC_EWORKSPACE.  Labels must
+ * lie in [0, V-1); an utterance with more labels than max_label_len gets no path. */
+size_t lc_ctc_align_workspace_bytes(int T, int B, int V, int max_label_len);
+int lc_ctc_align(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                 const int *seq_len, int max_label_len, int *ali, int *label_index, float *score,
+                 void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* tf.edit_distance(hyp, truth, normalize=False) — nnet/graph.py:143-149.  HOST function on HOST
  * buffers (integer DP on a few hundred tokens; SURVEY.md §2a keeps it on the host). */
 int lc_edit_distance_host(const int *hyp, int hyp_stride, const int *hyp_len, const int *truth,
@@ -407,6 +427,9 @@ int lc_debug_last_lstm_schedule(void);
 /* Same kind of hook for the CTC scan: device buffer of [2 phases][5 waves][512 iterations][8] 64-bit s_memtime stamps
  * of workgroup 0 (tools/ctc_stamps.py); NULL switches it off. */
 void lc_debug_set_ctc_stamps(unsigned long long *buf);
+/* Which of lc_ctc_align's three launches run (process-wide; tools/align_probe.py times them one by one on a workspace a
+ * full call has filled): bit 0 = per-frame log-sum-exp, bit 1 = forward sweep, bit 2 = backtrace.  Default 7. */
+void lc_debug_ctc_align_phases(int mask);
 /* A FOREIGN resident kernel for tests: `blocks` workgroups of 256 threads that stay resident for `microseconds` of wall
  * clock, hold `lds_bytes` of LDS each and do nothing else - what a collective's kernel waiting for a slower peer looks like
  * to the next persistent recurrence (one workgroup with >= 84 KB of LDS per CU on every CU of an XCD: with lds_bytes >= 80 KB

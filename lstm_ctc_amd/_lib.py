@@ -22,6 +22,10 @@ SIGNATURES = {
     "lc_ctc_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                             c_void_p, c_void_p, c_size_t, c_void_p]),
     "lc_ctc_greedy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lc_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "lc_ctc_align": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lc_debug_ctc_align_phases": (None, [c_int]),
     "lc_edit_distance_host": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lc_gemm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "lc_gemm_f32": (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int,

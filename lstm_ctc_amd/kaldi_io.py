@@ -74,3 +74,46 @@ def read_float_matrix_ark(path):
         out[key] = np.frombuffer(data[pos:pos + 4 * rows * cols], "<f4").reshape(rows, cols).copy()
         pos += 4 * rows * cols
     return out
+
+
+class Int32VectorWriter(BaseFloatMatrixWriter):
+    """Kaldi integer-vector table writer (what ``ali-to-phones`` / ``copy-int-vector`` read); wspecifiers as for
+    :class:`BaseFloatMatrixWriter`.  Binary entry (Kaldi's BasicVectorHolder<int32>): ``<key> `` ``\\0B`` one byte
+    ``\\x04`` (the size of the count) int32 count, then count little-endian int32 values as one block.  Text entry:
+    ``<key> v0 v1 ... \\n``."""
+
+    def Write(self, key, vector):
+        v = np.ascontiguousarray(vector, dtype=np.int32).reshape(-1)
+        self.ark.write((key + " ").encode())
+        if self.scp is not None:
+            self.scp.write("%s %s:%d\n" % (key, self.ark_path, self.ark.tell()))
+        if self.text:
+            self.ark.write(("".join("%d " % x for x in v.tolist()) + "\n").encode())
+        else:
+            self.ark.write(b"\0B" + b"\x04" + struct.pack("<i", v.size))
+            self.ark.write(v.astype("<i4").tobytes())
+        return True
+
+
+def read_int32_vector_ark(path, text=False):
+    """Minimal reader of the entries :class:`Int32VectorWriter` writes (tests / round trips): {key: int32 array}, in file
+    order."""
+    out = {}
+    with open(path, "rb") as f:
+        data = f.read()
+    if text:
+        for line in data.decode().splitlines():
+            key, _, rest = line.partition(" ")
+            out[key] = np.asarray([int(x) for x in rest.split()], np.int32)
+        return out
+    pos = 0
+    while pos < len(data):
+        sp = data.index(b" ", pos)
+        key = data[pos:sp].decode()
+        pos = sp + 1
+        assert data[pos:pos + 3] == b"\0B\x04", data[pos:pos + 3]
+        n = struct.unpack("<i", data[pos + 3:pos + 7])[0]
+        pos += 7
+        out[key] = np.frombuffer(data[pos:pos + 4 * n], "<i4").copy()
+        pos += 4 * n
+    return out

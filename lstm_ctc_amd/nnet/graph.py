@@ -332,6 +332,45 @@ class CTCGraph:
             out["grad_norm"] = float(self.norm_out[0].item())
         return out, 0
 
+    # ------------------------------------------------------------------------------------------------- forced alignment
+    def align(self, batch):
+        """Best-path (Viterbi) CTC alignment of one batch in the pipeline contract - no reference counterpart.  One forward
+        in inference mode (no dropout, batch-norm on its moving averages), then ``ops.ctc_align`` on the logits.  Returns
+        host arrays: ``ali`` [B,T] int32 (symbol per frame, blank = V-1; -1 beyond an utterance's length and when its labels
+        do not fit its frames), ``label_index`` [B,T] int32, ``score`` [B] float32 (-inf without a path) and
+        ``sequence_length``.  Never trains: parameters, ``global_step`` and the dropout stream are left as they were."""
+        x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = self._upload(batch)
+        self._validate_labels(flat)
+        model, dev = self.model, self.model.device
+        mode = (model.is_training, model.keep)
+        model.is_training, model.keep = False, 1.0
+        try:
+            def run():
+                ops.lstm_status(dev).zero_()
+                logits = model.forward(x, seq_d, seq_len_host=seq)
+                res = ops.ctc_align(logits, flat_d, offs_d, seq_d, maxlen)
+                return res, int(ops.lstm_status(dev).item())
+
+            if self._fallback.latched:
+                with ops.force_launch_train():
+                    res, status = run()
+            else:
+                res, status = run()
+                if status == 0:
+                    self._fallback.good()
+                else:                                      # a persistent launch could not complete: launch train
+                    self.persist_fallbacks += 1
+                    self._fallback.failed(status, self.persist_fallbacks)
+                    with ops.force_launch_train():
+                        res, status = run()
+            if status != 0:
+                raise RuntimeError("LSTM recurrence failed on the launch train as well (status %d)" % status)
+        finally:
+            model.is_training, model.keep = mode
+        ali, lidx, score = res
+        return {"ali": ali.cpu().numpy(), "label_index": lidx.cpu().numpy(), "score": score.cpu().numpy(),
+                "sequence_length": seq}
+
     def _apply_gradients(self):
         """L2 + clip_by_global_norm + optimizer.apply_gradients (graph.py:183-200), after the DP all-reduce.  The
         update is guarded by the LSTM status word: a step whose recurrence failed leaves parameters and slots alone.
@@ -448,6 +487,11 @@ def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group)
+
+
+def create_graph_for_alignment(pipeline, nnet_config, device="cuda"):
+    """A CTCGraph that is only asked to ``align`` (new, no reference counterpart): no optimizer, no dropout."""
+    return CTCGraph(pipeline, dict(nnet_config, is_training=False), device=device)
 
 
 def create_graph_for_inference(pipeline, nnet_config, smooth_factor=1.0, device="cuda"):

@@ -180,8 +180,8 @@ def create_pipeline_sequence_batch(dataset, input_dim, batch_size=64, batch_thre
 
 
 class SequentialPipeline:
-    def __init__(self, filename, tfrecord):
-        self.filename, self.tfrecord = filename, tfrecord
+    def __init__(self, filename, tfrecord, with_target=False):
+        self.filename, self.tfrecord, self.with_target = filename, tfrecord, with_target
 
     def __len__(self):
         return len(self.filename)
@@ -189,8 +189,11 @@ class SequentialPipeline:
     def __iter__(self):
         for name, path in zip(self.filename, self.tfrecord.files):
             item = self.tfrecord.load(path)
-            yield {"filename": name, "nnet_input": item["nnet_input"], "sequence_length": item["sequence_length"]}
+            out = {"filename": name, "nnet_input": item["nnet_input"], "sequence_length": item["sequence_length"]}
+            if self.with_target:              # new (forced alignment): the utterance's labels, empty when it has none
+                out["nnet_target"] = np.asarray(item.get("nnet_target", ()), np.int64).reshape(-1)
+            yield out
 
 
-def create_pipeline_sequential(filename, tfrecord, num_epochs=1):
-    return (lambda: None), SequentialPipeline(filename, tfrecord)
+def create_pipeline_sequential(filename, tfrecord, num_epochs=1, with_target=False):
+    return (lambda: None), SequentialPipeline(filename, tfrecord, with_target=with_target)

@@ -259,6 +259,48 @@ def ctc_loss(logits, labels, offsets, seq_len, max_label_len, want_grad=True):
     return loss, grad
 
 
+def ctc_align(logits, labels, offsets, seq_len, max_label_len, want_label_index=True):
+    """Best-path (Viterbi) forced alignment - no reference counterpart.  Arguments as for :func:`ctc_loss`.
+    Returns (ali [B,T] int32, label_index [B,T] int32 or None, score [B] f32) on the device: the symbol per frame
+    (blank = V-1), the index into the utterance's labels (-1 on blank frames) and the best path's log-probability;
+    -1 / -inf where an utterance has no path, -1 beyond seq_len."""
+    lib = _lib.load()
+    _require_cuda(logits, labels, offsets, seq_len)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
+    ali = torch.empty((B, T), dtype=torch.int32, device=logits.device)
+    lidx = torch.empty((B, T), dtype=torch.int32, device=logits.device) if want_label_index else None
+    score = torch.empty(B, dtype=torch.float32, device=logits.device)
+    nbytes = lib.lc_ctc_align_workspace_bytes(T, B, V, int(max_label_len))
+    ws = workspace("ctc_align", nbytes, logits.device)
+    if labels.numel() == 0:
+        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    _lib.check(lib.lc_ctc_align(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len),
+                                _ptr(ali), _ptr(lidx), _ptr(score), _ptr(ws), nbytes, _stream()), "lc_ctc_align")
+    return ali, lidx, score
+
+
+def alignment_segments(ali, label_index, seq_len):
+    """HOST function on numpy arrays: ali / label_index [B,T] and seq_len [B] as :func:`ctc_align` returns them ->
+    per utterance a list of (label, start_frame, num_frames) runs of non-blank frames.  A run ends where label_index
+    changes, so two equal labels in a row stay two segments."""
+    ali, label_index = np.asarray(ali), np.asarray(label_index)
+    out = []
+    for b in range(ali.shape[0]):
+        n = min(int(seq_len[b]), ali.shape[1])
+        segs, start = [], None
+        for t in range(n + 1):
+            cur = int(label_index[b, t]) if t < n else -1
+            if start is not None and cur != int(label_index[b, start]):
+                segs.append((int(ali[b, start]), start, t - start))
+                start = None
+            if start is None and cur >= 0:
+                start = t
+        out.append(segs)
+    return out
+
+
 def ctc_greedy(logits, seq_len):
     """Returns (tokens [B,T] int32, out_len [B] int32) on device."""
     lib = _lib.load()
