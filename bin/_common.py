@@ -48,6 +48,47 @@ def setup_device():
     return device, pg, rank, world
 
 
+def _fatal(msg):
+    sys.stderr.write("FATAL:tensorflow:" + msg + "\n")
+    sys.exit(1)
+
+
+def read_frame_targets(args):
+    """--objective xent: {utterance key: int32 vector} of --frame-targets, or the FATAL line and exit 1 when the flag is
+    missing or the table unreadable - which it also is when it names no utterance of <tfrecords.scp>.  None for every other
+    objective.  Host work only: runs BEFORE the device is set up, so a bad command line fails without touching a GPU."""
+    if args.objective != 'xent':
+        return None
+    spec = args.frame_targets
+    if not spec:
+        _fatal('--objective xent needs --frame-targets <rspecifier> (the table nnet-align writes)')
+    opts, sep, path = spec.partition(':')
+    if not sep:
+        opts, path = 'ark', spec
+    opts = [o.strip() for o in opts.split(',')]
+    if 'ark' not in opts or not path:
+        _fatal('--frame-targets: unsupported rspecifier (need ark:FILE, ark,t:FILE or a path): %s' % spec)
+    from lstm_ctc_amd.kaldi_io import read_int32_vector_ark
+    try:
+        table = read_int32_vector_ark(path, text='t' in opts)
+    except Exception as exc:                          # missing file, truncated or foreign content
+        _fatal('--frame-targets: cannot read "%s": %s: %s' % (path, type(exc).__name__, exc))
+    try:
+        keys = [os.path.splitext(os.path.basename(line.split()[4]))[0] for line in open(args.tfrecords_scp) if line.split()]
+    except (OSError, IndexError) as exc:
+        _fatal('cannot read "%s": %s' % (args.tfrecords_scp, exc))
+    if not any(k in table for k in keys):
+        _fatal('--frame-targets: "%s" (%d entries) names no utterance of "%s"' % (path, len(table), args.tfrecords_scp))
+    return table
+
+
+def report_frame_targets(pipeline):
+    """One INFO line at the end of a pass under --objective xent: the utterances that trained on nothing."""
+    from lstm_ctc_amd.nnet import tflog
+    tflog.info('frame targets: %d utterance(s) without an entry, %d with an entry of another length than their frames '
+               '(neither is scored)' % (pipeline.targets_missing, pipeline.targets_mismatched))
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:
@@ -68,9 +109,12 @@ POSITIONAL = {
     'alignment': ('<alignment-wspecifier>', 'Kaldi int32-vector table wspecifier for the per-frame symbols (new: nnet-align)'),
 }
 FLAGS = {
-    '--objective': dict(type=str, default='xent', help='training criterion; only "ctc" is implemented (the recipes pass it)'),
+    '--objective': dict(type=str, default='xent', help='training criterion: "ctc" (the recipes pass it), or "xent" = frame-level '
+                        'softmax cross-entropy against --frame-targets (new); the loss is then per frame and eval the frame error rate'),
+    '--frame-targets': dict(type=str, default=None, help='Kaldi int32-vector table rspecifier (ark:FILE, ark,t:FILE or a path) with one '
+                            'symbol per frame and utterance, as nnet-align writes it; required by --objective xent (new)'),
     '--optimizer': dict(type=str, default='sgd', help='sgd | momentum (0.9) | adam, constant learning rate'),
-    '--evaluate': dict(type=str2bool, default='false', help='also greedy-decode every batch and report the token error rate'),
+    '--evaluate': dict(type=str2bool, default='false', help='also report an error rate: greedy decoding and the token error rate (ctc), the frame error rate (xent)'),
     '--learn-rate': dict(type=float, default=0.0001, help='step size of the optimizer'),
     '--batch-size': dict(type=int, default=256, help='utterances per step (per GPU under torchrun)'),
     '--batch-threads': dict(type=int, default=8, help='batches assembled concurrently by the loader (capped at 4)'),

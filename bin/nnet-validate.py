@@ -3,11 +3,12 @@
 (main 26-92, flags 108-129)."""
 import sys
 
-from _common import build_cli, setup_device, quiet_unless_rank0
+from _common import build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets
 
 
 def run(args, init_only):
     try:
+        frame_targets = read_frame_targets(args)          # --objective xent only; fatal before the device is touched
         device, pg, rank, world = setup_device()
         import lstm_ctc_amd.nnet as nnet
         from lstm_ctc_amd.nnet import tflog
@@ -18,7 +19,7 @@ def run(args, init_only):
         filename, tfrecord, input_dim = nnet.dataset_from_tfrecords(
             tfrecords_scp=args.tfrecords_scp, left_context=nnet_config.get('left_context'),
             right_context=nnet_config.get('right_context'), subsample=nnet_config.get('subsample'), shuffle=False)
-        if args.objective != 'ctc':
+        if args.objective not in ('ctc', 'xent'):
             tflog.fatal('unsupported objective: %s' % args.objective)
             sys.exit(1)
         if nnet_type not in ('blstm', 'cudnnlstm', 'lstm'):
@@ -26,10 +27,11 @@ def run(args, init_only):
             sys.exit(1)
         _, pipeline = nnet.create_pipeline_sequence_batch(dataset=tfrecord, input_dim=input_dim,
                                                           batch_size=args.batch_size, batch_threads=args.batch_threads,
-                                                          rank=rank, world_size=world)
+                                                          rank=rank, world_size=world, frame_targets=frame_targets)
         # nnet-init sets no graph seed (bin/nnet-init.py:27-31): fresh random weights on every run
-        graph = nnet.create_graph_for_validation_ctc(pipeline=pipeline, nnet_config=nnet_config, device=device,
-                                                     seed=None if init_only else 123)
+        create_graph = (nnet.create_graph_for_validation_xent if args.objective == 'xent'
+                        else nnet.create_graph_for_validation_ctc)
+        graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, device=device, seed=None if init_only else 123)
         if init_only and pg is not None:                   # every rank must score the same random model
             from lstm_ctc_amd.nnet import dp
             dp.broadcast_(graph.model.ps.flat, pg, src=0)
@@ -38,6 +40,8 @@ def run(args, init_only):
             graph.restore(args.nnet_in)
         sess = nnet.Session(graph)
         nnet.validate(sess=sess, graph=graph, evaluate=args.evaluate, report_interval=args.report_interval)
+        if frame_targets is not None:
+            report_frame_targets(pipeline)
         if init_only and rank == 0:
             tflog.info('saving nnet to "%s"' % args.nnet_out)
             graph.save(args.nnet_out)
@@ -49,7 +53,8 @@ def run(args, init_only):
 
 def build_parser(init_only):
     return build_cli(('tfrecords_scp', 'nnet_config', 'nnet_out' if init_only else 'nnet_in'),
-                     ('--objective', '--evaluate', '--batch-size', '--batch-threads', '--report-interval'))
+                     ('--objective', '--evaluate', '--batch-size', '--batch-threads', '--report-interval',
+                      '--frame-targets'))
 
 
 if __name__ == '__main__':

@@ -86,6 +86,29 @@ int lc_ctc_align(const float *logits, int T, int B, int V, const int *labels, co
                  const int *seq_len, int max_label_len, int *ali, int *label_index, float *score,
                  void *workspace, size_t workspace_bytes, lc_stream_t stream);
 
+/* Frame-level softmax cross-entropy against one target symbol per frame - the objective that trains on what lc_ctc_align
+ * writes.  No reference counterpart (the reference never finished frame-level training).
+ *   logits [T,B,V] time-major fp32; targets [B,T] int32 (the layout of lc_ctc_align's ali); seq_len [B].
+ * A frame (t, b) is SCORED when t < seq_len[b] and 0 <= targets[b,t] < V.  Class V-1 (the blank) is a legal target here;
+ * -1 means "ignore".
+ *   loss [B]     sum over scored frames of -log_softmax(logits[t,b,:])[target], natural log;
+ *   frames [B]   number of scored frames;
+ *   correct [B]  scored frames whose argmax equals the target (lowest index among equal maxima: lc_ctc_greedy's rule);
+ *   grad [T,B,V] or NULL: d sum_b loss[b] / d logits = softmax - onehot on scored rows, +0 on every other row;
+ *                un-normalised, the convention of lc_ctc_loss.
+ * A live target < -1 or >= V makes loss[b] NaN (lc_ctc_loss's convention for bad labels); its frame counts nowhere and gets
+ * a zero row.  -inf logits behave as in float arithmetic: a -inf non-target class contributes 0 and gets gradient 0, a -inf
+ * target gives +inf loss, an all -inf row gives NaN.
+ * Every element of loss, frames, correct and grad is written on every call (no memset needed); results are bit-identical
+ * from call to call (no atomics: the per-frame terms go to the workspace - 8 bytes per frame - and a second launch folds
+ * each utterance's terms in a fixed order in double and rounds once to float).  Arithmetic per frame: one fp32 log-sum-exp
+ * and one fp32 subtraction.  Rows of V <= 1024 are read once and kept in registers up to the gradient store (V <= 64: four
+ * frames per wave); wider rows are re-read.  T, B <= 0, V < 2 or a NULL required pointer: LC_EINVAL with no launch; a
+ * workspace below lc_xent_workspace_bytes: LC_EWORKSPACE.  Elements are indexed in 64 bits (T * B * V may exceed 2^31). */
+size_t lc_xent_workspace_bytes(int T, int B, int V);
+int lc_xent_loss(const float *logits, int T, int B, int V, const int *targets, const int *seq_len, float *loss,
+                 int *frames, int *correct, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* tf.edit_distance(hyp, truth, normalize=False) — nnet/graph.py:143-149.  HOST function on HOST
  * buffers (integer DP on a few hundred tokens; SURVEY.md §2a keeps it on the host). */
 int lc_edit_distance_host(const int *hyp, int hyp_stride, const int *hyp_len, const int *truth,

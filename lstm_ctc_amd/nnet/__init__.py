@@ -10,7 +10,8 @@ from .pipeline import create_pipeline_sequence_batch, create_pipeline_sequential
 from .tfrecord import dataset_from_tfrecords, write_tfrecord
 
 __all__ = ["parse_config", "get_class_prior", "train", "validate", "create_graph_for_inference",
-           "create_graph_for_training_ctc", "create_graph_for_validation_ctc", "create_graph_for_alignment", "Session",
+           "create_graph_for_training_ctc", "create_graph_for_validation_ctc", "create_graph_for_alignment",
+           "create_graph_for_training_xent", "create_graph_for_validation_xent", "Session",
            "get_create_logits", "create_logits_blstm", "create_logits_lstm", "create_logits_cudnnlstm",
            "create_pipeline_sequence_batch", "create_pipeline_sequential", "dataset_from_tfrecords",
            "write_tfrecord"]
@@ -21,7 +22,8 @@ def __getattr__(name):
         from . import funcs
         return getattr(funcs, name)
     if name in ("create_graph_for_inference", "create_graph_for_training_ctc", "create_graph_for_validation_ctc",
-                "create_graph_for_alignment", "Session", "OutOfRangeError", "get_create_logits", "create_logits_blstm", "create_logits_lstm",
+                "create_graph_for_alignment", "create_graph_for_training_xent", "create_graph_for_validation_xent",
+                "Session", "OutOfRangeError", "get_create_logits", "create_logits_blstm", "create_logits_lstm",
                 "create_logits_cudnnlstm"):
         from . import graph
         return getattr(graph, name)

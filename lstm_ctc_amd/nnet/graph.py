@@ -132,13 +132,22 @@ class _FallbackLatch:
 
 
 class CTCGraph:
-    """Validation (and, with ``learn_rate``, training) graph over a batch pipeline."""
+    """Validation (and, with ``learn_rate``, training) graph over a batch pipeline.
+
+    ``objective="ctc"`` is the reference's criterion.  ``objective="xent"`` (new, no reference counterpart) is the frame-level
+    softmax cross-entropy against ``batch["frame_target"]`` [B,T] int32 (one symbol per frame as ``align`` writes them, the
+    blank included; -1 = ignore): ``size`` is then the number of scored frames, ``eval_loss`` their summed -log p(target),
+    ``eval`` the number of them the argmax gets wrong - so the run loops log the mean loss per frame and the frame error
+    rate - and ``nnet_target`` is not read."""
 
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
-                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None):
+                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc"):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
+        if objective not in ("ctc", "xent"):
+            raise ValueError("unsupported objective: %s" % objective)
+        self.objective = objective
         self.pipeline = pipeline
         self.model = Model(nnet_config, device, seed=seed)
         self.training = learn_rate is not None
@@ -203,6 +212,34 @@ class CTCGraph:
         d = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)
         return x, d(seq), seq, d(flat), d(offs), flat, offs, maxlen
 
+    def _upload_frame_target(self, batch):
+        """objective = xent: (device [B,T] int32, the same on the host) of ``batch["frame_target"]``.  A pure copy."""
+        ft = np.ascontiguousarray(batch["frame_target"], dtype=np.int32)
+        return torch.from_numpy(ft).to(self.model.device, non_blocking=True), ft
+
+    def _raise_together(self, bad, mine, theirs):
+        """Under data parallelism every rank must leave the step together (a rank that raised alone would strand the others
+        in the gradient collectives), so the verdict is summed over the group first."""
+        if self.pg is not None and self.world > 1:
+            flag = torch.tensor([int(bad)], dtype=torch.int32, device=self.model.device)
+            dp.allreduce_sum_(flag, self.pg)
+            bad_anywhere = int(flag.item()) != 0
+        else:
+            bad_anywhere = bad
+        if bad_anywhere:
+            raise ValueError(mine() if bad else theirs)
+
+    def _validate_frame_targets(self, ft, seq):
+        """objective = xent: a live frame's target must lie in [-1, V) (-1 = ignore; the blank V - 1 is a legal target).  Like
+        _validate_labels: for the batch being CONSUMED, one verdict for all ranks.  (The kernel alone would turn such a target
+        into a NaN loss.)"""
+        V = self.model.ps.V
+        live = ft[np.arange(ft.shape[1])[None, :] < np.asarray(seq)[:, None]] if ft.size else ft.reshape(-1)
+        bad = bool(live.size and (int(live.min()) < -1 or int(live.max()) >= V))
+        self._raise_together(bad, lambda: "frame_target holds a symbol outside [-1, %d): min %d, max %d (num_targets = %d)"
+                             % (V, int(live.min()), int(live.max()), V),
+                             "another rank's frame_target holds a symbol outside [-1, %d)" % V)
+
     def _validate_labels(self, flat):
         """tf.nn.ctc_loss raises InvalidArgument for labels outside [0, num_classes - 1) (the blank, V - 1, is not a label).
         Done in ``step`` for the batch being CONSUMED - not while batch k + 1 is staged, which would raise before step k has
@@ -211,17 +248,9 @@ class CTCGraph:
         is summed over the group first."""
         V = self.model.ps.V
         bad = bool(flat.size and (int(flat.min()) < 0 or int(flat.max()) >= V - 1))
-        if self.pg is not None and self.world > 1:
-            flag = torch.tensor([int(bad)], dtype=torch.int32, device=self.model.device)
-            dp.allreduce_sum_(flag, self.pg)
-            bad_anywhere = int(flag.item()) != 0
-        else:
-            bad_anywhere = bad
-        if bad_anywhere:
-            if bad:
-                raise ValueError("nnet_target holds a label outside [0, %d): min %d, max %d (num_targets = %d, "
-                                 "blank = %d)" % (V - 1, int(flat.min()), int(flat.max()), V, V - 1))
-            raise ValueError("another rank's nnet_target holds a label outside [0, %d)" % (V - 1))
+        self._raise_together(bad, lambda: "nnet_target holds a label outside [0, %d): min %d, max %d (num_targets = %d, "
+                             "blank = %d)" % (V - 1, int(flat.min()), int(flat.max()), V, V - 1),
+                             "another rank's nnet_target holds a label outside [0, %d)" % (V - 1))
 
     def stage(self, batch):
         """Uploads ``batch`` on a side stream NOW, to be consumed by a later ``step(None, staged=...)``: called for batch
@@ -232,6 +261,8 @@ class CTCGraph:
             self._h2d_stream = torch.cuda.Stream(dev)
         with torch.cuda.stream(self._h2d_stream):
             up = self._upload(batch)
+            if self.objective == "xent":
+                up = up + self._upload_frame_target(batch)
             ev = torch.cuda.Event()
             ev.record()
         return up, ev
@@ -249,25 +280,35 @@ class CTCGraph:
                     t.record_stream(cur)          # allocated on the copy stream, consumed on this one
         else:
             up = self._upload(batch)
-        x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = up
-        self._validate_labels(flat)
+            if self.objective == "xent":
+                up = up + self._upload_frame_target(batch)
+        x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = up[:8]
+        ft_d = None
+        if self.objective == "xent":                  # reads no nnet_target: has_label = 0 corpora are fine
+            ft_d, ft = up[8:]
+            self._validate_frame_targets(ft, seq)
+        else:
+            self._validate_labels(flat)
         out = self.step_device(x, seq_d, flat_d, offs_d, maxlen, int(len(flat)), fetch_eval=fetch_eval,
-                               fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs, seq_host=seq)
+                               fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs, seq_host=seq,
+                               frame_target=ft_d)
         out["sequence_length"] = seq
         return out
 
     def step_device(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval=False, fetch_logits=False, train=None,
-                    flat_host=None, offs_host=None, seq_host=None):
+                    flat_host=None, offs_host=None, seq_host=None, frame_target=None):
         """The same step on tensors already resident in HBM: x [T,B,D] time-major f32, seq_d [B] i32,
         labels flat i32 + offsets [B+1] i32.  seq_host: seq_d's values on the host, when the caller has them (pack_frames
-        then builds a new batch's frame map without a device-to-host copy).
+        then builds a new batch's frame map without a device-to-host copy).  frame_target: [B,T] i32 on the device, the
+        targets of objective = xent (labels / offsets / size are then not used).
 
         A persistent-recurrence launch that cannot complete (lstm_ctc_hip.h: bounded waits, sticky status word) leaves
         NaN outputs and makes the optimizer skip its update on the device; the word is read at the step's one sync
         point and the step is then re-run, in this process, with the per-step launch train."""
         train = self.training if train is None else train
         counters = (self.global_step, self.drop_seed, self.opt_step)
-        args = (x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host, seq_host)
+        args = (x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host, seq_host,
+                frame_target)
         if self._fallback.latched:                     # co-residency is structurally unavailable: stay on the train
             with ops.force_launch_train():
                 out, status = self._step_once(*args)
@@ -288,12 +329,14 @@ class CTCGraph:
         return out
 
     def _step_once(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
-                   seq_host=None):
+                   seq_host=None, frame_target=None):
         dev = self.model.device
         ops.lstm_status(dev).zero_()
         self.global_step += 1
         self.drop_seed = (self.drop_seed * 1664525 + 1013904223) & 0x7FFFFFFF
         logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed, seq_len_host=seq_host)      # [T,B,V]
+        if self.objective == "xent":
+            return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train)
         loss_b, grad = ops.ctc_loss(logits, flat_d, offs_d, seq_d, maxlen, want_grad=train)
         out = {"size": size}
         tokens = out_len = None
@@ -330,6 +373,47 @@ class CTCGraph:
             out["logits"] = logits.permute(1, 0, 2).cpu().numpy()                # reference layout [B,T,V]
         if train:
             out["grad_norm"] = float(self.norm_out[0].item())
+        return out, 0
+
+    def _finish_xent(self, logits, seq_d, frame_target, fetch_eval, fetch_logits, train):
+        """The rest of a step under objective = xent: ``ops.xent_loss`` in the place of ``ops.ctc_loss``; regulariser,
+        backward, L2, clip, optimizer and status word as in the CTC step.  A batch without a scored frame (size 0) still
+        runs the optimizer step - on a zero loss gradient - so that ranks stay in lockstep."""
+        if frame_target is None:
+            raise ValueError("objective = xent needs frame_target (create_pipeline_sequence_batch(..., frame_targets=...))")
+        dev = self.model.device
+        loss_b, frames, correct, grad = ops.xent_loss(logits, frame_target, seq_d, want_grad=train)
+        reg = None
+        if self.sm_weight > 0:
+            T_, B_, V_ = logits.shape
+            reg = ops.label_smoothing(logits.view(T_ * B_, V_), self.sm_weight, self.sm_logq,
+                                      grad.view(T_ * B_, V_) if train else None)
+        bn_saved = None
+        if train:
+            bn_saved = dict(self.model.saved.get("bn") or {})
+            self._buckets = (dp.GradientBuckets(self.model.ps.grad, self.pg)
+                             if self.pg is not None and self.dp_buckets and (self.world > 1 or self._force_buckets) else None)
+            self.model.backward(grad, buckets=self._buckets)
+            self._apply_gradients()
+        # everything the host wants, in ONE device->host copy: the step's single sync
+        f64 = lambda t: t.to(torch.float64).sum().view(1)
+        zero = torch.zeros(1, dtype=torch.float64, device=dev)
+        word = torch.cat([f64(loss_b), f64(frames), f64(correct), f64(ops.lstm_status(dev)),
+                          reg.to(torch.float64).view(1) if reg is not None else zero,
+                          self.norm_out[:1].to(torch.float64) if train else zero]).cpu().numpy()
+        status = int(word[3])
+        if status != 0:
+            return None, status
+        if train and bn_saved:
+            self.model.update_moving_averages(bn_saved)
+        n_frames = int(word[1])
+        out = {"size": n_frames, "eval_loss": float(word[0]), "loss": float(word[0]) + float(word[4])}
+        if fetch_eval:
+            out["eval"] = float(n_frames - int(word[2]))          # frames the argmax gets wrong
+        if fetch_logits:
+            out["logits"] = logits.permute(1, 0, 2).cpu().numpy()
+        if train:
+            out["grad_norm"] = float(word[5])
         return out, 0
 
     # ------------------------------------------------------------------------------------------------- forced alignment
@@ -487,6 +571,18 @@ def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group)
+
+
+def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None):
+    """Frame cross-entropy against the pipeline's ``frame_target`` (new, no reference counterpart)."""
+    return CTCGraph(pipeline, nnet_config, device=device, seed=seed, objective="xent")
+
+
+def create_graph_for_training_xent(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
+                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None):
+    return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
+                    l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
+                    objective="xent")
 
 
 def create_graph_for_alignment(pipeline, nnet_config, device="cuda"):

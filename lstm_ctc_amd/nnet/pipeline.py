@@ -20,6 +20,7 @@ of a step is world_size consecutive batches.  All ranks see the same number of s
 dropped) so the collectives line up.
 """
 import ctypes
+import os
 import queue
 import threading
 import weakref
@@ -77,15 +78,44 @@ class _HostBuffers:
 
 class SequenceBatchPipeline:
     def __init__(self, dataset, input_dim, batch_size, rank=0, world_size=1, prefetch=4, batch_threads=2,
-                 num_parallel_calls=None):
+                 num_parallel_calls=None, frame_targets=None):
         self.dataset, self.input_dim, self.batch_size = dataset, input_dim, batch_size
+        # frame-level targets (new, the xent objective): {utterance key: int32 vector, one symbol per frame}; the key is the
+        # TFRecord file's basename without extension, what nnet-align / nnet-forward write.  Utterances without an entry, or
+        # whose entry does not have the utterance's frame count (after splice / subsample), are counted and get no target.
+        self.frame_targets = frame_targets
+        self.targets_missing = self.targets_mismatched = 0
+        self._count_lock = threading.Lock()
         self.rank, self.world_size, self.prefetch = rank, world_size, max(1, prefetch)
         self.batch_threads = max(1, min(int(batch_threads or 1), 4))
         npc = num_parallel_calls if num_parallel_calls is not None else getattr(dataset, "num_parallel_calls", 8)
         self.num_parallel_calls = max(1, int(npc))
 
     # ------------------------------------------------------------------------------------------ one batch
-    def _collate(self, items):
+    @staticmethod
+    def utterance_key(path):
+        """The table key of an utterance: its TFRecord file's basename without extension (bin/nnet-align.py)."""
+        return os.path.splitext(os.path.basename(path))[0]
+
+    def _frame_target(self, paths, frames, T):
+        """``frame_target`` of a batch: [B, T] int32, row b = the table entry of utterance b, -1 behind it; an all -1 row for
+        an utterance without an entry or with one of another length than its ``frames[b]`` (both counted)."""
+        out = np.full((len(paths), T), -1, np.int32)
+        missing = mismatched = 0
+        for b, path in enumerate(paths):
+            v = self.frame_targets.get(self.utterance_key(path))
+            if v is None:
+                missing += 1
+            elif len(v) != int(frames[b]):
+                mismatched += 1
+            else:
+                out[b, :len(v)] = v
+        with self._count_lock:
+            self.targets_missing += missing
+            self.targets_mismatched += mismatched
+        return out
+
+    def _collate(self, items, paths=None):
         """Padding of already-loaded utterance dicts (any dataset with ``load``): the generic, copying form."""
         B = len(items)
         T = max(int(it["sequence_length"]) for it in items)
@@ -96,14 +126,19 @@ class SequenceBatchPipeline:
             x[b, :it["nnet_input"].shape[0]] = it["nnet_input"]
             if "nnet_target" in it:
                 y[b, :len(it["nnet_target"])] = it["nnet_target"]
-        return {"nnet_input": x, "nnet_target": y,
-                "sequence_length": np.asarray([it["sequence_length"] for it in items], np.int32),
-                "target_length": np.asarray([it.get("target_length", 0) for it in items], np.int32)}
+        batch = {"nnet_input": x, "nnet_target": y,
+                 "sequence_length": np.asarray([it["sequence_length"] for it in items], np.int32),
+                 "target_length": np.asarray([it.get("target_length", 0) for it in items], np.int32)}
+        if self.frame_targets is not None:
+            if paths is None:
+                raise ValueError("frame_targets need the utterances' paths (their keys)")
+            batch["frame_target"] = self._frame_target(paths, batch["sequence_length"], T)
+        return batch
 
     def _assemble(self, paths, pool, buffers):
         ds = self.dataset
         if not hasattr(ds, "open_batch"):                                       # any dataset with ``load``
-            return self._collate(list(pool.map(ds.load, paths)))
+            return self._collate(list(pool.map(ds.load, paths)), paths)
         nb = ds.open_batch(paths, self.num_parallel_calls)                      # read + CRC + counts, native threads
         B, D = len(paths), self.input_dim
         T = int(nb.frames.max()) if B else 0
@@ -113,8 +148,11 @@ class SequenceBatchPipeline:
         nb.decode(flat, D, B * D, T, y if ds.has_label else None)               # copy + splice / subsample + padding
         if not ds.has_label:
             y = np.full((B, 0), -1, np.int64)
-        return {"nnet_input": flat.reshape(T, B, D).transpose(1, 0, 2), "nnet_target": y,
-                "sequence_length": nb.frames.copy(), "target_length": nb.labels.copy()}
+        batch = {"nnet_input": flat.reshape(T, B, D).transpose(1, 0, 2), "nnet_target": y,
+                 "sequence_length": nb.frames.copy(), "target_length": nb.labels.copy()}
+        if self.frame_targets is not None:
+            batch["frame_target"] = self._frame_target(paths, nb.frames, T)
+        return batch
 
     def _starts(self):
         n = len(self.dataset)
@@ -173,10 +211,12 @@ class SequenceBatchPipeline:
 
 
 def create_pipeline_sequence_batch(dataset, input_dim, batch_size=64, batch_threads=8, num_epochs=1, rank=0,
-                                   world_size=1, num_parallel_calls=None):
-    """Returns (initializer, pipeline) like the reference; the initializer is a no-op callable."""
+                                   world_size=1, num_parallel_calls=None, frame_targets=None):
+    """Returns (initializer, pipeline) like the reference; the initializer is a no-op callable.  ``frame_targets`` (new):
+    {utterance key: int32 vector}; every batch then carries ``frame_target`` [B, T] int32 padded with -1."""
     return (lambda: None), SequenceBatchPipeline(dataset, input_dim, batch_size, rank, world_size,
-                                                 batch_threads=batch_threads, num_parallel_calls=num_parallel_calls)
+                                                 batch_threads=batch_threads, num_parallel_calls=num_parallel_calls,
+                                                 frame_targets=frame_targets)
 
 
 class SequentialPipeline:

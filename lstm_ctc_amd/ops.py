@@ -281,6 +281,35 @@ def ctc_align(logits, labels, offsets, seq_len, max_label_len, want_label_index=
     return ali, lidx, score
 
 
+def xent_loss(logits, targets, seq_len, want_grad=True):
+    """Frame-level softmax cross-entropy - no reference counterpart.  logits [T,B,V] f32; targets [B,T] int32, one symbol
+    per frame as :func:`ctc_align` writes them (the blank V-1 is a legal target, -1 = ignore); seq_len [B] int32.
+    Returns (loss [B] f32, frames [B] int32, correct [B] int32, grad [T,B,V] or None) on the device: the summed
+    -log_softmax[target] of the scored frames (t < seq_len[b], 0 <= target < V), their number, how many of them the
+    argmax gets right, and d sum(loss) / d logits (zero rows on frames that are not scored)."""
+    lib = _lib.load()
+    _require_cuda(logits, targets, seq_len)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    assert targets.dtype == torch.int32 and seq_len.dtype == torch.int32
+    if tuple(targets.shape) != (B, T) or seq_len.numel() != B:
+        raise ValueError("xent_loss: targets must be [B, T] = [%d, %d] and seq_len [B] (got %s, %s)"
+                         % (B, T, tuple(targets.shape), tuple(seq_len.shape)))
+    targets = targets.contiguous()
+    dev = logits.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    correct = torch.empty(B, dtype=torch.int32, device=dev)
+    grad = torch.empty_like(logits) if want_grad else None
+    nbytes = lib.lc_xent_workspace_bytes(T, B, V)
+    ws = workspace("xent", nbytes, dev)
+    ev = _prof_begin()
+    _lib.check(lib.lc_xent_loss(_ptr(logits), T, B, V, _ptr(targets), _ptr(seq_len), _ptr(loss), _ptr(frames),
+                                _ptr(correct), _ptr(grad), _ptr(ws), nbytes, _stream()), "lc_xent_loss")
+    _prof_end("xent", (T, B, V), ev)
+    return loss, frames, correct, grad
+
+
 def alignment_segments(ali, label_index, seq_len):
     """HOST function on numpy arrays: ali / label_index [B,T] and seq_len [B] as :func:`ctc_align` returns them ->
     per utterance a list of (label, start_frame, num_frames) runs of non-blank frames.  A run ends where label_index
