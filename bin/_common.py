@@ -54,10 +54,19 @@ def _fatal(msg):
 
 
 def read_frame_targets(args):
-    """--objective xent: {utterance key: int32 vector} of --frame-targets, or the FATAL line and exit 1 when the flag is
-    missing or the table unreadable - which it also is when it names no utterance of <tfrecords.scp>.  None for every other
-    objective.  Host work only: runs BEFORE the device is set up, so a bad command line fails without touching a GPU."""
-    if args.objective != 'xent':
+    """--objective xent, or --objective ctc with --align-window: {utterance key: int32 vector} of --frame-targets, or the FATAL
+    line and exit 1 when the flag is missing or the table unreadable - which it also is when it names no utterance of
+    <tfrecords.scp> - and when --align-window is negative or meets another objective than ctc.  None for every other
+    command line.  Host work only: runs BEFORE the device is set up, so a bad command line fails without touching a GPU."""
+    window = getattr(args, 'align_window', None)
+    if window is not None:
+        if args.objective != 'ctc':
+            _fatal('--align-window constrains the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
+        if window < 0:
+            _fatal('--align-window must be a number of frames >= 0, got %d' % window)
+        if not args.frame_targets:
+            _fatal('--align-window needs --frame-targets <rspecifier> (the table nnet-align writes)')
+    elif args.objective != 'xent':
         return None
     spec = args.frame_targets
     if not spec:
@@ -89,6 +98,14 @@ def report_frame_targets(pipeline):
                '(neither is scored)' % (pipeline.targets_missing, pipeline.targets_mismatched))
 
 
+def report_label_windows(graph):
+    """One INFO line at the end of a pass under --align-window: how many utterances the windows reached."""
+    from lstm_ctc_amd.nnet import tflog
+    tflog.info('label windows (+-%d frames): %d utterance(s) constrained, %d unconstrained (no entry, another length, or an '
+               'alignment that does not spell the labels)'
+               % (graph.align_window, graph.windows_constrained, graph.windows_unconstrained))
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:
@@ -113,6 +130,9 @@ FLAGS = {
                         'softmax cross-entropy against --frame-targets (new); the loss is then per frame and eval the frame error rate'),
     '--frame-targets': dict(type=str, default=None, help='Kaldi int32-vector table rspecifier (ark:FILE, ark,t:FILE or a path) with one '
                             'symbol per frame and utterance, as nnet-align writes it; required by --objective xent (new)'),
+    '--align-window': dict(type=int, default=None, help='with --objective ctc and --frame-targets: sum the CTC criterion only over '
+                           'paths that keep every label within this many frames of where the alignment table puts it (new); '
+                           'utterances the table does not cover train on plain CTC'),
     '--optimizer': dict(type=str, default='sgd', help='sgd | momentum (0.9) | adam, constant learning rate'),
     '--evaluate': dict(type=str2bool, default='false', help='also report an error rate: greedy decoding and the token error rate (ctc), the frame error rate (xent)'),
     '--learn-rate': dict(type=float, default=0.0001, help='step size of the optimizer'),

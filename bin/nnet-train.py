@@ -4,12 +4,13 @@ mobvoi/lstm_ctc bin/nnet-train.py (flags 113-151, main 26-100), so scripts/train
 Launch under ``python -m torch.distributed.run --nproc-per-node N`` for utterance-batch data parallelism."""
 import sys
 
-from _common import build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets
+from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
+                     report_label_windows)
 
 
 def main(args):
     try:
-        frame_targets = read_frame_targets(args)          # --objective xent only; fatal before the device is touched
+        frame_targets = read_frame_targets(args)          # xent, or ctc with --align-window; fatal before the device is touched
         device, pg, rank, world = setup_device()
         import lstm_ctc_amd.nnet as nnet
         from lstm_ctc_amd.nnet import tflog
@@ -31,14 +32,17 @@ def main(args):
                                                           batch_size=args.batch_size, batch_threads=args.batch_threads,
                                                           rank=rank, world_size=world, frame_targets=frame_targets)
         create_graph = nnet.create_graph_for_training_xent if args.objective == 'xent' else nnet.create_graph_for_training_ctc
+        windowed = {'align_window': args.align_window} if args.align_window is not None else {}
         graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, learn_rate=args.learn_rate,
                              clip_norm=args.clip_norm, optimizer=args.optimizer, device=device, seed=args.seed,
-                             process_group=pg)
+                             process_group=pg, **windowed)
         graph.restore(args.nnet_in)                       # trainable variables only; Adam slots restart
         sess = nnet.Session(graph)
         nnet.train(sess=sess, graph=graph, evaluate=args.evaluate, report_interval=args.report_interval)
         if frame_targets is not None:
             report_frame_targets(pipeline)
+        if args.align_window is not None:
+            report_label_windows(graph)
         if rank == 0:
             tflog.info('saving nnet to "%s"' % args.nnet_out)
             graph.save(args.nnet_out)
@@ -52,6 +56,6 @@ if __name__ == '__main__':
     args = build_cli(('tfrecords_scp', 'nnet_config', 'nnet_in', 'nnet_out'),
                      ('--objective', '--optimizer', '--evaluate', '--learn-rate', '--batch-size', '--batch-threads',
                       '--seed', '--num-parallel-calls', '--report-interval', '--shuffle', '--clip-norm',
-                      '--frame-targets')).parse_args()
+                      '--frame-targets', '--align-window')).parse_args()
     sys.stderr.write('INFO:tensorflow:' + ' '.join(sys.argv) + '\n')
     main(args)

@@ -3,12 +3,13 @@
 (main 26-92, flags 108-129)."""
 import sys
 
-from _common import build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets
+from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
+                     report_label_windows)
 
 
 def run(args, init_only):
     try:
-        frame_targets = read_frame_targets(args)          # --objective xent only; fatal before the device is touched
+        frame_targets = read_frame_targets(args)          # xent, or ctc with --align-window; fatal before the device is touched
         device, pg, rank, world = setup_device()
         import lstm_ctc_amd.nnet as nnet
         from lstm_ctc_amd.nnet import tflog
@@ -31,7 +32,10 @@ def run(args, init_only):
         # nnet-init sets no graph seed (bin/nnet-init.py:27-31): fresh random weights on every run
         create_graph = (nnet.create_graph_for_validation_xent if args.objective == 'xent'
                         else nnet.create_graph_for_validation_ctc)
-        graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, device=device, seed=None if init_only else 123)
+        align_window = getattr(args, 'align_window', None)      # nnet-init has no such flag
+        windowed = {'align_window': align_window} if align_window is not None else {}
+        graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, device=device, seed=None if init_only else 123,
+                             **windowed)
         if init_only and pg is not None:                   # every rank must score the same random model
             from lstm_ctc_amd.nnet import dp
             dp.broadcast_(graph.model.ps.flat, pg, src=0)
@@ -42,6 +46,8 @@ def run(args, init_only):
         nnet.validate(sess=sess, graph=graph, evaluate=args.evaluate, report_interval=args.report_interval)
         if frame_targets is not None:
             report_frame_targets(pipeline)
+        if align_window is not None:
+            report_label_windows(graph)
         if init_only and rank == 0:
             tflog.info('saving nnet to "%s"' % args.nnet_out)
             graph.save(args.nnet_out)
@@ -54,7 +60,7 @@ def run(args, init_only):
 def build_parser(init_only):
     return build_cli(('tfrecords_scp', 'nnet_config', 'nnet_out' if init_only else 'nnet_in'),
                      ('--objective', '--evaluate', '--batch-size', '--batch-threads', '--report-interval',
-                      '--frame-targets'))
+                      '--frame-targets') + (() if init_only else ('--align-window',)))
 
 
 if __name__ == '__main__':

@@ -86,6 +86,31 @@ int lc_ctc_align(const float *logits, int T, int B, int V, const int *labels, co
                  const int *seq_len, int max_label_len, int *ali, int *label_index, float *score,
                  void *workspace, size_t workspace_bytes, lc_stream_t stream);
 
+/* Alignment-windowed CTC: lc_ctc_loss summed only over the paths that keep every label inside a window of frames - the
+ * criterion that bounds emission times with the alignment lc_ctc_align writes.  No reference counterpart.  Everything not
+ * said here is lc_ctc_loss's contract (logits [T,B,V] time-major fp32, flat int32 labels + label_offsets [B+1], blank = V-1,
+ * ctc_merge_repeated transitions, a path starts in position 0 or 1 and ends in S-1 or S-2, grad may be NULL).
+ *   win_lo, win_hi  device int32, parallel to labels: label j of utterance b may occupy frame t only when
+ *                   win_lo[j] <= t <= win_hi[j].  Blank positions are never constrained.  Values outside [0, seq_len[b])
+ *                   are legal and clip ("unconstrained" is lo <= 0, hi >= T-1); lo > hi is a label with no frame: no path.
+ *   loss [B]        -log of the total softmax probability of the surviving paths, natural log;
+ *   grad [T,B,V]    softmax - occupancy over the surviving paths on live frames, +0 for t >= seq_len[b]; un-normalised.
+ * Conventions of lc_ctc_loss: more labels than frames or seq_len <= 0 -> loss 0, gradient 0; a label outside [0, V-1) (or
+ * more labels than max_label_len) -> loss NaN, gradient 0; no surviving path (labels do not fit, an empty window, windows no
+ * monotone path satisfies) -> loss +inf, gradient = softmax on the live frames, no NaN anywhere; L = 0 -> the all-blank path.
+ * Every element of loss and grad is written on every call (no memset needed); results are bit-identical from call to call
+ * (no atomics, fixed summation orders).  Arithmetic: fp32 log-softmax emissions; the lattice cells are doubles in the log2
+ * domain (the log-sum-exp of a cell's predecessors on the fp32 exp2 / log2 pipes relative to their maximum, the additions
+ * in double), so a cell's error does not grow with its magnitude; log p and the occupancy exponents are formed in double
+ * and rounded once.
+ * Shapes: lc_ctc_loss's (T, B > 0, V >= 2, 0 <= max_label_len <= 1023); anything else or a NULL required pointer is
+ * LC_EINVAL with no launch, a workspace below lc_ctc_window_workspace_bytes (0 for a bad shape) is LC_EWORKSPACE.  Elements
+ * are indexed in 64 bits.  The workspace holds both lattices: about 2 * T * B * roundup(2 * max_label_len + 1, 64) doubles. */
+size_t lc_ctc_window_workspace_bytes(int T, int B, int V, int max_label_len);
+int lc_ctc_loss_windowed(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                         const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
+                         float *loss, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* Frame-level softmax cross-entropy against one target symbol per frame - the objective that trains on what lc_ctc_align
  * writes.  No reference counterpart (the reference never finished frame-level training).
  *   logits [T,B,V] time-major fp32; targets [B,T] int32 (the layout of lc_ctc_align's ali); seq_len [B].

@@ -138,16 +138,30 @@ class CTCGraph:
     softmax cross-entropy against ``batch["frame_target"]`` [B,T] int32 (one symbol per frame as ``align`` writes them, the
     blank included; -1 = ignore): ``size`` is then the number of scored frames, ``eval_loss`` their summed -log p(target),
     ``eval`` the number of them the argmax gets wrong - so the run loops log the mean loss per frame and the frame error
-    rate - and ``nnet_target`` is not read."""
+    rate - and ``nnet_target`` is not read.
+
+    ``align_window=N`` (new, ``objective="ctc"`` only; an int >= 0) is alignment-windowed CTC: the criterion is summed only
+    over the paths that keep every label within N frames of the run ``batch["frame_target"]`` gives it
+    (``ops.label_windows`` on the host, ``ops.ctc_loss_windowed`` where the step calls ``ops.ctc_loss``); an utterance whose
+    row is all -1 or does not spell its labels trains on plain CTC.  ``windows_constrained`` / ``windows_unconstrained``
+    count the utterances of either kind.  ``None`` is the unwindowed step, untouched."""
 
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
-                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc"):
+                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
         if objective not in ("ctc", "xent"):
             raise ValueError("unsupported objective: %s" % objective)
         self.objective = objective
+        if align_window is not None:
+            if objective != "ctc":
+                raise ValueError("align_window constrains the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
+            if isinstance(align_window, bool) or not isinstance(align_window, (int, np.integer)) or align_window < 0:
+                raise ValueError("align_window must be an int >= 0 (frames) or None, got %r" % (align_window,))
+            align_window = int(align_window)
+        self.align_window = align_window
+        self.windows_constrained = self.windows_unconstrained = 0
         self.pipeline = pipeline
         self.model = Model(nnet_config, device, seed=seed)
         self.training = learn_rate is not None
@@ -217,6 +231,17 @@ class CTCGraph:
         ft = np.ascontiguousarray(batch["frame_target"], dtype=np.int32)
         return torch.from_numpy(ft).to(self.model.device, non_blocking=True), ft
 
+    def _upload_windows(self, batch, flat, offs, seq):
+        """align_window: (win_lo, win_hi on the device, constrained [B] on the host) from ``batch["frame_target"]``; (None,
+        None, None) when the batch carries none (``step`` raises for that).  A pure function of the batch plus copies:
+        ``ops.label_windows`` never raises for content."""
+        ft = batch.get("frame_target")
+        if ft is None:
+            return None, None, None
+        lo, hi, constrained = ops.label_windows(np.asarray(ft), flat, offs, seq, self.align_window, self.model.ps.V - 1)
+        d = lambda a: torch.from_numpy(a).to(self.model.device, non_blocking=True)
+        return d(lo), d(hi), constrained
+
     def _raise_together(self, bad, mine, theirs):
         """Under data parallelism every rank must leave the step together (a rank that raised alone would strand the others
         in the gradient collectives), so the verdict is summed over the group first."""
@@ -263,6 +288,8 @@ class CTCGraph:
             up = self._upload(batch)
             if self.objective == "xent":
                 up = up + self._upload_frame_target(batch)
+            elif self.align_window is not None:
+                up = up + self._upload_windows(batch, up[5], up[6], up[2])
             ev = torch.cuda.Event()
             ev.record()
         return up, ev
@@ -282,33 +309,47 @@ class CTCGraph:
             up = self._upload(batch)
             if self.objective == "xent":
                 up = up + self._upload_frame_target(batch)
+            elif self.align_window is not None:
+                up = up + self._upload_windows(batch, up[5], up[6], up[2])
         x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = up[:8]
-        ft_d = None
+        ft_d = windows = None
         if self.objective == "xent":                  # reads no nnet_target: has_label = 0 corpora are fine
             ft_d, ft = up[8:]
             self._validate_frame_targets(ft, seq)
         else:
             self._validate_labels(flat)
+            if self.align_window is not None:
+                lo_d, hi_d, constrained = up[8:]
+                if lo_d is None:
+                    raise ValueError("align_window needs frame_target in the batch "
+                                     "(create_pipeline_sequence_batch(..., frame_targets=...))")
+                windows = (lo_d, hi_d)
+                self.windows_constrained += int(constrained.sum())
+                self.windows_unconstrained += int(len(constrained) - constrained.sum())
         out = self.step_device(x, seq_d, flat_d, offs_d, maxlen, int(len(flat)), fetch_eval=fetch_eval,
                                fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs, seq_host=seq,
-                               frame_target=ft_d)
+                               frame_target=ft_d, windows=windows)
         out["sequence_length"] = seq
         return out
 
     def step_device(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval=False, fetch_logits=False, train=None,
-                    flat_host=None, offs_host=None, seq_host=None, frame_target=None):
+                    flat_host=None, offs_host=None, seq_host=None, frame_target=None, windows=None):
         """The same step on tensors already resident in HBM: x [T,B,D] time-major f32, seq_d [B] i32,
         labels flat i32 + offsets [B+1] i32.  seq_host: seq_d's values on the host, when the caller has them (pack_frames
         then builds a new batch's frame map without a device-to-host copy).  frame_target: [B,T] i32 on the device, the
-        targets of objective = xent (labels / offsets / size are then not used).
+        targets of objective = xent (labels / offsets / size are then not used).  windows: (win_lo, win_hi) int32 on the device,
+        parallel to the labels - required when the graph was built with align_window.
 
         A persistent-recurrence launch that cannot complete (lstm_ctc_hip.h: bounded waits, sticky status word) leaves
         NaN outputs and makes the optimizer skip its update on the device; the word is read at the step's one sync
         point and the step is then re-run, in this process, with the per-step launch train."""
         train = self.training if train is None else train
         counters = (self.global_step, self.drop_seed, self.opt_step)
+        if self.align_window is not None and windows is None:
+            raise ValueError("align_window needs the label windows (step: frame_target in the batch, frame_targets= of the "
+                             "pipeline; step_device: windows=)")
         args = (x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host, seq_host,
-                frame_target)
+                frame_target, windows)
         if self._fallback.latched:                     # co-residency is structurally unavailable: stay on the train
             with ops.force_launch_train():
                 out, status = self._step_once(*args)
@@ -329,7 +370,7 @@ class CTCGraph:
         return out
 
     def _step_once(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
-                   seq_host=None, frame_target=None):
+                   seq_host=None, frame_target=None, windows=None):
         dev = self.model.device
         ops.lstm_status(dev).zero_()
         self.global_step += 1
@@ -337,7 +378,11 @@ class CTCGraph:
         logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed, seq_len_host=seq_host)      # [T,B,V]
         if self.objective == "xent":
             return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train)
-        loss_b, grad = ops.ctc_loss(logits, flat_d, offs_d, seq_d, maxlen, want_grad=train)
+        if self.align_window is not None:
+            loss_b, grad = ops.ctc_loss_windowed(logits, flat_d, offs_d, seq_d, maxlen, windows[0], windows[1],
+                                                 want_grad=train)
+        else:
+            loss_b, grad = ops.ctc_loss(logits, flat_d, offs_d, seq_d, maxlen, want_grad=train)
         out = {"size": size}
         tokens = out_len = None
         reg = None
@@ -563,14 +608,15 @@ def load_params(ps, path):
 
 
 # ----------------------------------------------------------------------------------------------------- reference-named factories
-def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None):
-    return CTCGraph(pipeline, nnet_config, device=device, seed=seed)
+def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None, align_window=None):
+    return CTCGraph(pipeline, nnet_config, device=device, seed=seed, align_window=align_window)
 
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
-                                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None):
+                                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
-                    l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group)
+                    l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
+                    align_window=align_window)
 
 
 def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None):

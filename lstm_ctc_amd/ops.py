@@ -259,6 +259,84 @@ def ctc_loss(logits, labels, offsets, seq_len, max_label_len, want_grad=True):
     return loss, grad
 
 
+def ctc_loss_windowed(logits, labels, offsets, seq_len, max_label_len, win_lo, win_hi, want_grad=True):
+    """Alignment-windowed CTC - no reference counterpart.  Arguments as for :func:`ctc_loss`, plus win_lo / win_hi: int32
+    on the device, parallel to the flat labels; label j may sit on frame t only when win_lo[j] <= t <= win_hi[j] (values
+    outside the utterance clip; see :func:`label_windows`).  Returns (loss[B], grad[T,B,V] or None) over the surviving paths;
+    +inf and a softmax gradient where no path survives."""
+    lib = _lib.load()
+    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
+    assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
+    if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
+        raise ValueError("ctc_loss_windowed: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
+                         % (win_lo.numel(), win_hi.numel(), labels.numel()))
+    win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits) if want_grad else None
+    nbytes = lib.lc_ctc_window_workspace_bytes(T, B, V, int(max_label_len))
+    ws = workspace("ctc_window", nbytes, logits.device)
+    if labels.numel() == 0:
+        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
+        win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
+        win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    ev = _prof_begin()
+    _lib.check(lib.lc_ctc_loss_windowed(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len),
+                                        int(max_label_len), _ptr(win_lo), _ptr(win_hi), _ptr(loss), _ptr(grad), _ptr(ws),
+                                        nbytes, _stream()), "lc_ctc_loss_windowed")
+    _prof_end("ctc", (T, B, V), ev)
+    return loss, grad
+
+
+WINDOW_OPEN = np.iinfo(np.int32).max
+
+
+def label_windows(frame_target, flat, offsets, seq_len, tau, blank):
+    """HOST function on numpy arrays: the windows :func:`ctc_loss_windowed` takes, from a frame-level alignment.
+    frame_target [B,T] int32 is one symbol per frame as :func:`ctc_align` writes it (``blank`` on blank frames, -1 = no
+    entry); flat / offsets are the flattened labels, seq_len [B] the frame counts.  Returns (win_lo, win_hi, constrained):
+    two int32 vectors parallel to ``flat`` and a bool per utterance.
+
+    For utterance b, take the maximal runs of equal non-blank symbols in frame_target[b, :seq_len[b]].  If the row holds no
+    -1 and the runs' symbols spell the utterance's labels exactly (a valid CTC path separates equal neighbours by a blank,
+    so runs and labels correspond one to one; no labels and an all-blank row qualify), label i gets
+    [first frame of run i - tau, last frame of run i + tau].  Otherwise - an all -1 row, which is what the pipeline hands
+    out for a missing or wrong-length entry, or any row that does not spell the labels - the utterance stays unconstrained
+    (lo = 0, hi = INT32_MAX) and constrained[b] is False.  Never raises for content."""
+    frame_target = np.asarray(frame_target)
+    flat = np.asarray(flat).reshape(-1)
+    offsets = np.asarray(offsets).reshape(-1)
+    B = len(offsets) - 1
+    tau = int(tau)
+    lo = np.zeros(flat.shape[0], np.int32)
+    hi = np.full(flat.shape[0], WINDOW_OPEN, np.int32)
+    constrained = np.zeros(B, bool)
+    T = frame_target.shape[1] if frame_target.ndim == 2 else 0
+    for b in range(B):
+        o0, o1 = int(offsets[b]), int(offsets[b + 1])
+        n = min(max(int(seq_len[b]), 0), T)
+        if frame_target.ndim != 2 or b >= frame_target.shape[0] or o1 < o0:
+            continue
+        row = frame_target[b, :n].astype(np.int64)
+        if row.size and row.min() < 0:
+            continue
+        # run starts: a non-blank frame whose predecessor holds another symbol
+        nb = row != blank
+        start = nb.copy()
+        start[1:] &= row[1:] != row[:-1]
+        end = nb.copy()
+        end[:-1] &= row[1:] != row[:-1]
+        first, last = np.flatnonzero(start), np.flatnonzero(end)
+        if len(first) != o1 - o0 or not np.array_equal(row[first], flat[o0:o1].astype(np.int64)):
+            continue
+        lo[o0:o1] = np.maximum(first - tau, np.iinfo(np.int32).min)
+        hi[o0:o1] = np.minimum(last + tau, WINDOW_OPEN)
+        constrained[b] = True
+    return lo, hi, constrained
+
+
 def ctc_align(logits, labels, offsets, seq_len, max_label_len, want_label_index=True):
     """Best-path (Viterbi) forced alignment - no reference counterpart.  Arguments as for :func:`ctc_loss`.
     Returns (ali [B,T] int32, label_index [B,T] int32 or None, score [B] f32) on the device: the symbol per frame
