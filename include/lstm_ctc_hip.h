@@ -54,7 +54,12 @@ int lc_get_option(const char *name, long *value);
  *   logits [T,B,V]; labels flat int32; label_offsets [B+1]; seq_len [B];
  *   max_label_len: host-side max_b (offsets[b+1]-offsets[b]);
  *   loss [B] (= -log p; 0 for skipped utterances, +inf when no valid path);
- *   grad [T,B,V] or NULL (d sum(loss) / d logits; 0 beyond seq_len). */
+ *   grad [T,B,V] or NULL (d sum(loss) / d logits; 0 beyond seq_len).
+ * Shapes: T, B > 0, V >= 2, 0 <= max_label_len <= 1023; with a gradient V <= 10240 (alphabets above 128 classes keep four
+ * rows of per-class sums in LDS, 16 V bytes of the 160 KB a workgroup can hold; a loss-only call has no such limit).
+ * Anything else or a NULL required pointer is LC_EINVAL, a workspace below lc_ctc_workspace_bytes LC_EWORKSPACE; both
+ * launch nothing and leave loss and grad untouched.  Every element of loss and grad is written by a successful call,
+ * whatever the workspace held before. */
 size_t lc_ctc_workspace_bytes(int T, int B, int V, int max_label_len);
 int lc_ctc_loss(const float *logits, int T, int B, int V, const int *labels,
                 const int *label_offsets, const int *seq_len, int max_label_len, float *loss,
@@ -475,6 +480,13 @@ int lc_debug_last_lstm_schedule(void);
 /* Same kind of hook for the CTC scan: device buffer of [2 phases][5 waves][512 iterations][8] 64-bit s_memtime stamps
  * of workgroup 0 (tools/ctc_stamps.py); NULL switches it off. */
 void lc_debug_set_ctc_stamps(unsigned long long *buf);
+/* Which kernels the calling thread's last SUCCESSFUL lc_ctc_loss call dispatched (tests assert it); 0 before the first:
+ *   bits 0-3    1 = two launches of the meet-in-the-middle kernel, 2 = three kernels (row statistics, scan, gradient)
+ *   bits 4-9    PPL, lattice positions per lane of the scan      bits 10-13  NW, scan waves per direction
+ *   bits 14-17  KG, classes per lane of the frame waves (3: V <= 48, 5: V <= 80, 8: V <= 128; 0 on the three-kernel path)
+ *   bit 18      the frame statistics were taken in phase 2 ("ctc_lse2")
+ *   bits 19-25  lanes per frame of the row-statistics kernel (three-kernel path: 16 for V <= 32, else 64). */
+int lc_debug_last_ctc_path(void);
 /* Which of lc_ctc_align's three launches run (process-wide; tools/align_probe.py times them one by one on a workspace a
  * full call has filled): bit 0 = per-frame log-sum-exp, bit 1 = forward sweep, bit 2 = backtrace.  Default 7. */
 void lc_debug_ctc_align_phases(int mask);

@@ -16,7 +16,8 @@
 //                      per-segment offset kept in double.  Logit gathers are prefetched 8 steps ahead.
 //   3. ctc_grad        one wave per (t,b) frame: posterior mass per class from alpha+beta-logp (per-segment
 //                      offsets), label positions through wave-private LDS float atomics, blank positions through a
-//                      wave reduction; grad = softmax - posterior.  All independent loads are issued up front.
+//                      wave reduction; grad = softmax - posterior / (the frame's total posterior mass).  All independent
+//                      loads are issued up front.
 #include "common.h"
 #include <stdlib.h>
 
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
     for (int w = 0; w < 4; ++w) cav[w] = ca[min(w, nw - 1)];
     const bool live = inrange && t < Tb && st != 1;
     const int U = 2 * (off1 - off0) + 1;
-    float blank_acc = 0.f;
+    float blank_acc = 0.f, label_acc = 0.f;
     if (live && st == 0) {
         // stored rows are re-centred per lattice segment (one scan wave each): log2(alpha*beta/p) = a + b +
         // (offset_a + offset_b - log2 p), the bracket summed in double per segment
@@ -527,11 +528,20 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
             const float e0 = __builtin_amdgcn_exp2f(av.x + bv.x - lp), e1 = __builtin_amdgcn_exp2f(av.y + bv.y - lp);
             const float e2 = __builtin_amdgcn_exp2f(av.z + bv.z - lp), e3 = __builtin_amdgcn_exp2f(av.w + bv.w - lp);
             blank_acc += e0 + ((u0 + 2 < U) ? e2 : 0.f);
+            label_acc += ((u0 + 1 < U) ? e1 : 0.f) + ((u0 + 3 < U) ? e3 : 0.f);
             if (u0 + 1 < U) atomicAdd(&bins[l1], e1);
             if (u0 + 3 < U) atomicAdd(&bins[l3], e3);
         }
     }
     blank_acc = lc_wave_sum(blank_acc);
+    label_acc = lc_wave_sum(label_acc);
+    // sum_u alpha_t[u] beta_t[u] = p at EVERY frame, so a frame's occupancies sum to 1 - up to the roundings the two fp32
+    // recursions gathered on their way to it, which grow with a cell's distance from its row maximum (an utterance with
+    // hardly more frames than labels lives hundreds of log2 units below it: the sums were 2.5e-3 off at T_b = 1356,
+    // L = 1023).  That error is common to the frame's cells: divide it out by the frame's own total instead of trusting
+    // log p (largest gradient error of tests/test_gpu_ctc_edges.py's batch at T = 701, L = 512: 9.3e-4 before, 1.2e-4 now).
+    const float tot = blank_acc + label_acc;
+    const float inv = tot > 0.f ? 1.f / tot : 0.f;
     if (inrange) {
         float *g = grad + (size_t)row * V;
         if (!live) {
@@ -540,7 +550,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
             for (int k = lane; k < V; k += 64) {
                 const float xv = (k == lane) ? x0 : x[k];
                 const float y = expf(xv - lse);
-                const float p = (st == 2) ? 0.f : ((k == V - 1) ? blank_acc : bins[k]);
+                const float p = (st == 2) ? 0.f : ((k == V - 1) ? blank_acc : bins[k]) * inv;
                 g[k] = y - p;
             }
         }
@@ -943,7 +953,9 @@ __device__ __forceinline__ void mm_frames_load(MmFrames<KG, NP> &f, int base, in
     const int g = lane >> 4, l = lane & 15;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-        const int s = max(min(base + 4 * q + g, n - 1), 0), t = dir == 0 ? tt0 + s : tt0 - s;
+        // n == 0 (the beta workgroup's second half of a one-frame utterance: tt0 = -1): t would be -1, a row in front of
+        // the utterance's first; nothing of such a load is used, but it must stay inside the tensor
+        const int s = max(min(base + 4 * q + g, n - 1), 0), t = max(dir == 0 ? tt0 + s : tt0 - s, 0);
         const float *row = xb + (size_t)t * rowstride;
 #pragma unroll
         for (int k = 0; k < KG; ++k) f.x[q][k] = row[min(l + 16 * k, V - 1)];
@@ -1517,6 +1529,13 @@ static size_t ctc_legacy_workspace_bytes(int T, int B, int max_label_len)
 // Development hook (not part of the product surface): device buffer of [2 phases][5 waves][512 iterations][8] s_memtime
 // stamps of workgroup 0 (tools/ctc_stamps.py).
 extern "C" void lc_debug_set_ctc_stamps(unsigned long long *buf) { g_ctc_dbg = buf; }
+// Development hook: which kernels the calling thread's last successful lc_ctc_loss dispatched (lstm_ctc_hip.h; tests assert it)
+static thread_local int g_last_ctc_path = 0;
+static inline int ctc_path_word(int path, int ppl, int nw, int kg, int lse2, int g)
+{
+    return path | ppl << 4 | nw << 10 | kg << 14 | lse2 << 18 | g << 19;
+}
+extern "C" int lc_debug_last_ctc_path(void) { return g_last_ctc_path; }
 
 extern "C" size_t lc_ctc_workspace_bytes(int T, int B, int V, int max_label_len)
 {
@@ -1546,14 +1565,17 @@ static int mm_launch(const MmArgs &a, int B, int V, hipStream_t s)
     if (a.lse2) hipLaunchKernelGGL((ctc_mm_kernel<PPL, NW, KG, 3>), dim3(nblk), dim3((NW + mm_nf(NW)) * 64), lds2, s, a);
     else hipLaunchKernelGGL((ctc_mm_kernel<PPL, NW, KG, 2>), dim3(nblk), dim3((NW + mm_nf(NW)) * 64), lds2, s, a);
     LC_CHECK_LAUNCH("ctc_mm");
+    g_last_ctc_path = ctc_path_word(1, PPL, NW, KG, a.lse2, 0);
     return LC_OK;
 }
 
+#define CTC_GRAD_MAX_V 10240      /* 4 waves x V float bins = the 160 KB of LDS a gfx950 workgroup can hold */
+static inline int row_stats_group(int V) { return V <= 32 ? 16 : 64; }      // lanes per frame
 static void launch_row_stats(const float *logits, int T, int B, int V, const int *seq_len, float *rmax,
                              float *rlse, int *argmax, hipStream_t s)
 {
     const size_t rows = (size_t)T * B;
-    if (V <= 32) {
+    if (row_stats_group(V) == 16) {
         const int G = 16;
         hipLaunchKernelGGL(ctc_row_stats_kernel<G>, dim3(lc_cdiv(rows * G, 256)), dim3(256), 0, s, logits, T, B, V,
                            seq_len, rmax, rlse, argmax);
@@ -1572,6 +1594,9 @@ extern "C" int lc_ctc_loss(const float *logits, int T, int B, int V, const int *
     LC_CHECK_ARG(T > 0 && B > 0 && V >= 2 && max_label_len >= 0, "lc_ctc_loss: bad shape T=%d B=%d V=%d L=%d", T, B, V, max_label_len);
     const int S = 2 * max_label_len + 1;
     LC_CHECK_ARG(S <= 64 * 32, "lc_ctc_loss: label length %d exceeds the supported maximum 1023", max_label_len);
+    // ctc_grad_kernel keeps one bin per class for each of its four waves in LDS (160 KB per workgroup on gfx950)
+    LC_CHECK_ARG(!grad || V <= CTC_GRAD_MAX_V, "lc_ctc_loss: a gradient over %d classes exceeds the supported maximum %d", V,
+                 CTC_GRAD_MAX_V);
     if (workspace_bytes < lc_ctc_workspace_bytes(T, B, V, max_label_len)) {
         lc_set_error("lc_ctc_loss: workspace too small (%zu < %zu)", workspace_bytes,
                      lc_ctc_workspace_bytes(T, B, V, max_label_len));
@@ -1631,6 +1656,14 @@ extern "C" int lc_ctc_loss(const float *logits, int T, int B, int V, const int *
     float *alpha = (float *)w; w += lat;
     float *beta = (float *)w;
 
+    const size_t grad_lds = 4 * (size_t)V * sizeof(float);
+    if (grad && grad_lds > 64 * 1024 &&          // before the first launch: a refused call leaves loss and grad untouched
+        hipFuncSetAttribute((const void *)ctc_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)grad_lds) !=
+            hipSuccess) {
+        (void)hipGetLastError();
+        lc_set_error("lc_ctc_loss: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %zu) failed", grad_lds);
+        return LC_ELAUNCH;
+    }
     launch_row_stats(logits, T, B, V, seq_len, rmax, rlse, nullptr, s);
     LC_CHECK_LAUNCH("ctc_row_stats");
     const int nw = ctc_nw(S), ppl = ctc_ppl(S);
@@ -1651,10 +1684,11 @@ extern "C" int lc_ctc_loss(const float *logits, int T, int B, int V, const int *
 #undef LC_SCAN
     LC_CHECK_LAUNCH("ctc_scan");
     if (grad) {
-        hipLaunchKernelGGL(ctc_grad_kernel, dim3(lc_cdiv(rows, 4)), dim3(256), 4 * V * sizeof(float), s, logits, T,
+        hipLaunchKernelGGL(ctc_grad_kernel, dim3(lc_cdiv(rows, 4)), dim3(256), grad_lds, s, logits, T,
                            B, V, labels, label_offsets, seq_len, rlse, alpha, beta, srow, coffa, coffb, ngroups, nw, 64 * ppl, logp2, status, grad);
         LC_CHECK_LAUNCH("ctc_grad");
     }
+    g_last_ctc_path = ctc_path_word(2, ppl, nw, 0, 0, row_stats_group(V));
     return LC_OK;
 }
 

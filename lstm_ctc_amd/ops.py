@@ -125,6 +125,14 @@ def last_lstm_schedule():
                 dz_shadow_in_kernel=bool(v >> 18 & 1))
 
 
+def last_ctc_path():
+    """Decoded lc_debug_last_ctc_path(): dict(path, ppl, nw, kg, lse2, g) of this thread's last successful ctc_loss."""
+    v = _lib.load().lc_debug_last_ctc_path()
+    paths = {0: "none", 1: "two_launch", 2: "three_kernel"}
+    return dict(path=paths.get(v & 0xf, "?"), ppl=(v >> 4) & 0x3f, nw=(v >> 10) & 0xf, kg=(v >> 14) & 0xf,
+                lse2=bool(v >> 18 & 1), g=(v >> 19) & 0x7f)
+
+
 def _f32c(t):
     assert t.dtype == torch.float32, t.dtype
     return t if t.is_contiguous() else t.contiguous()

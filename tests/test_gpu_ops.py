@@ -353,14 +353,16 @@ def test_greedy_tf_known_answers(ops):
 
 
 @pytest.mark.parametrize("T,B,V,Lmin,Lmax", [
-    (30, 5, 6, 1, 8),          # PPL 1
-    (120, 9, 44, 10, 50),      # PPL 2
-    (300, 8, 72, 60, 120),     # PPL 4
-    (600, 4, 44, 150, 250),    # PPL 8
-    (1100, 3, 30, 300, 500),   # PPL 16
-    (1400, 2, 20, 520, 560),   # PPL 32
+    # <positions per lane, scan waves> as lc_debug_last_ctc_path reports them (tests/test_gpu_ctc_edges.py asserts the hook
+    # on every geometry; the comments here name what these shapes take)
+    (30, 5, 6, 1, 8),          # two launches <1, 1>: at most 64 lattice positions
+    (120, 9, 44, 10, 50),      # two launches <1, 2>: at most 128
+    (300, 8, 72, 60, 120),     # two launches <1, 4>: at most 256, classes 49 .. 80 (KG = 5)
+    (600, 4, 44, 150, 250),    # three kernels, scan <2, 4>: 257 .. 512 positions at B <= 128
+    (1100, 3, 30, 300, 500),   # three kernels, scan <4, 4>: 513 .. 1024 positions at B <= 128, row statistics 16 lanes wide
+    (1400, 2, 20, 520, 560),   # three kernels, scan <8, 4>: beyond 1024 positions at any B
     # more than 128 utterances: the many-utterance geometries of the two-launch path (B <= 128 with more than 256 lattice
-    # positions, and every lattice beyond 1024 positions, take the three-kernel path: the cases above from PPL 8 on)
+    # positions, and every lattice beyond 1024 positions, take the three-kernel path: the three cases above)
     (60, 130, 9, 3, 14),       # one scan wave, 4 positions per lane (the B = 512 bench geometry)
     (300, 131, 44, 90, 126),   # the same at its widest (253 positions)
     (340, 129, 20, 130, 160),  # four scan waves x 2 positions per lane, per-class LDS atomics
