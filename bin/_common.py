@@ -91,6 +91,64 @@ def read_frame_targets(args):
     return table
 
 
+def read_teacher_scores(args):
+    """--teacher-scores: the lazily read table (kaldi_io.FloatMatrixTable) of the teacher's per-frame scores, or None without
+    the flag.  The FATAL line and exit 1 for --objective kd without the flag, a weight or temperature that is not a
+    positive finite number, an unsupported rspecifier, an unreadable table and a table that names no utterance of
+    <tfrecords.scp>.  Host work only: runs BEFORE the device is set up."""
+    spec = getattr(args, 'teacher_scores', None)
+    if args.objective == 'kd' and not spec:
+        _fatal('--objective kd needs --teacher-scores <rspecifier> (the table nnet-forward --apply-log writes)')
+    import math
+    for flag, value in (('--teacher-weight', getattr(args, 'teacher_weight', 1.0)),
+                        ('--teacher-temperature', getattr(args, 'teacher_temperature', 1.0))):
+        if not (math.isfinite(value) and value > 0):
+            _fatal('%s must be a finite number > 0, got %r' % (flag, value))
+    if not spec:
+        return None
+    if args.teacher_domain not in ('log', 'prob'):
+        _fatal('--teacher-domain must be "log" or "prob", got "%s"' % args.teacher_domain)
+    opts, sep, path = spec.partition(':')
+    if not sep:
+        opts, path = 'ark', spec
+    opts = [o.strip() for o in opts.split(',')]
+    if 'ark' not in opts or not path:
+        _fatal('--teacher-scores: unsupported rspecifier (need ark:FILE, ark,t:FILE or a path): %s' % spec)
+    from lstm_ctc_amd.kaldi_io import FloatMatrixTable
+    try:
+        table = FloatMatrixTable(path, text='t' in opts)
+    except Exception as exc:                          # missing file, truncated or foreign content
+        _fatal('--teacher-scores: cannot read "%s": %s: %s' % (path, type(exc).__name__, exc))
+    try:
+        keys = [os.path.splitext(os.path.basename(line.split()[4]))[0] for line in open(args.tfrecords_scp) if line.split()]
+    except (OSError, IndexError) as exc:
+        _fatal('cannot read "%s": %s' % (args.tfrecords_scp, exc))
+    if not any(k in table for k in keys):
+        _fatal('--teacher-scores: "%s" (%d entries) names no utterance of "%s"' % (path, len(table), args.tfrecords_scp))
+    return table
+
+
+def teacher_keywords(args, table, nnet_config):
+    """(pipeline keywords, graph keywords) of the teacher flags; both empty without --teacher-scores."""
+    if table is None:
+        return {}, {}
+    graph = {'teacher_temperature': args.teacher_temperature}
+    if args.objective != 'kd':
+        graph['teacher_weight'] = args.teacher_weight
+    return ({'teacher_scores': table, 'teacher_domain': args.teacher_domain, 'num_targets': nnet_config.get('num_targets')},
+            graph)
+
+
+def report_teacher_scores(pipeline, graph):
+    """One INFO line at the end of a pass with --teacher-scores: the utterances the table did not cover and how the student
+    compares on the frames it did."""
+    from lstm_ctc_amd.nnet import tflog
+    n, a = graph.kd_frames_total, graph.kd_agree_total
+    tflog.info('teacher scores: %d utterance(s) without an entry, %d with an entry of another shape than [frames, targets], '
+               '%d with a row that is no distribution (none is scored); %d frame(s) scored, the argmaxes agree on %.2f%%'
+               % (pipeline.teacher_missing, pipeline.teacher_mismatched, pipeline.teacher_bad, n, 100.0 * a / max(n, 1)))
+
+
 def report_frame_targets(pipeline):
     """One INFO line at the end of a pass under --objective xent: the utterances that trained on nothing."""
     from lstm_ctc_amd.nnet import tflog
@@ -127,7 +185,14 @@ POSITIONAL = {
 }
 FLAGS = {
     '--objective': dict(type=str, default='xent', help='training criterion: "ctc" (the recipes pass it), or "xent" = frame-level '
-                        'softmax cross-entropy against --frame-targets (new); the loss is then per frame and eval the frame error rate'),
+                        'softmax cross-entropy against --frame-targets (new); the loss is then per frame and eval the frame error rate; '
+                        'or "kd" = distillation from --teacher-scores alone (new): loss per frame, eval the argmax disagreement rate'),
+    '--teacher-scores': dict(type=str, default=None, help='Kaldi float-matrix table rspecifier (ark:FILE, ark,t:FILE or a path) with the '
+                             'teacher\'s per-frame scores [frames, targets], as nnet-forward --apply-log writes them (new); adds '
+                             'weight * T^2 * KL(teacher || student) to --objective ctc / xent, required by --objective kd'),
+    '--teacher-domain': dict(type=str, default='log', help='"log": the table holds log-posteriors or logits; "prob": probabilities (new)'),
+    '--teacher-weight': dict(type=float, default=1.0, help='weight of the distillation term beside --objective ctc / xent (new)'),
+    '--teacher-temperature': dict(type=float, default=1.0, help='temperature T both distributions are softened with (new)'),
     '--frame-targets': dict(type=str, default=None, help='Kaldi int32-vector table rspecifier (ark:FILE, ark,t:FILE or a path) with one '
                             'symbol per frame and utterance, as nnet-align writes it; required by --objective xent (new)'),
     '--align-window': dict(type=int, default=None, help='with --objective ctc and --frame-targets: sum the CTC criterion only over '

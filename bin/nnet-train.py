@@ -5,12 +5,13 @@ Launch under ``python -m torch.distributed.run --nproc-per-node N`` for utteranc
 import sys
 
 from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
-                     report_label_windows)
+                     report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores)
 
 
 def main(args):
     try:
         frame_targets = read_frame_targets(args)          # xent, or ctc with --align-window; fatal before the device is touched
+        teacher = read_teacher_scores(args)               # --teacher-scores / --objective kd; likewise
         device, pg, rank, world = setup_device()
         import lstm_ctc_amd.nnet as nnet
         from lstm_ctc_amd.nnet import tflog
@@ -22,25 +23,30 @@ def main(args):
             tfrecords_scp=args.tfrecords_scp, left_context=nnet_config.get('left_context'),
             right_context=nnet_config.get('right_context'), subsample=nnet_config.get('subsample'),
             shuffle=args.shuffle, seed=args.seed, num_parallel_calls=args.num_parallel_calls)
-        if args.objective not in ('ctc', 'xent'):
+        if args.objective not in ('ctc', 'xent', 'kd'):
             tflog.fatal('unsupported objective: %s' % args.objective)
             sys.exit(1)
         if nnet_type not in ('blstm', 'cudnnlstm', 'lstm'):
             tflog.fatal('unsupported nnet_type: %s' % nnet_type)
             sys.exit(1)
+        teacher_pipe, teacher_graph = teacher_keywords(args, teacher, nnet_config)
         _, pipeline = nnet.create_pipeline_sequence_batch(dataset=tfrecord, input_dim=input_dim,
                                                           batch_size=args.batch_size, batch_threads=args.batch_threads,
-                                                          rank=rank, world_size=world, frame_targets=frame_targets)
-        create_graph = nnet.create_graph_for_training_xent if args.objective == 'xent' else nnet.create_graph_for_training_ctc
+                                                          rank=rank, world_size=world, frame_targets=frame_targets,
+                                                          **teacher_pipe)
+        create_graph = {'xent': nnet.create_graph_for_training_xent, 'kd': nnet.create_graph_for_training_kd}.get(
+            args.objective, nnet.create_graph_for_training_ctc)
         windowed = {'align_window': args.align_window} if args.align_window is not None else {}
         graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, learn_rate=args.learn_rate,
                              clip_norm=args.clip_norm, optimizer=args.optimizer, device=device, seed=args.seed,
-                             process_group=pg, **windowed)
+                             process_group=pg, **windowed, **teacher_graph)
         graph.restore(args.nnet_in)                       # trainable variables only; Adam slots restart
         sess = nnet.Session(graph)
         nnet.train(sess=sess, graph=graph, evaluate=args.evaluate, report_interval=args.report_interval)
         if frame_targets is not None:
             report_frame_targets(pipeline)
+        if teacher is not None:
+            report_teacher_scores(pipeline, graph)
         if args.align_window is not None:
             report_label_windows(graph)
         if rank == 0:
@@ -56,6 +62,7 @@ if __name__ == '__main__':
     args = build_cli(('tfrecords_scp', 'nnet_config', 'nnet_in', 'nnet_out'),
                      ('--objective', '--optimizer', '--evaluate', '--learn-rate', '--batch-size', '--batch-threads',
                       '--seed', '--num-parallel-calls', '--report-interval', '--shuffle', '--clip-norm',
-                      '--frame-targets', '--align-window')).parse_args()
+                      '--frame-targets', '--align-window', '--teacher-scores', '--teacher-domain', '--teacher-weight',
+                      '--teacher-temperature')).parse_args()
     sys.stderr.write('INFO:tensorflow:' + ' '.join(sys.argv) + '\n')
     main(args)

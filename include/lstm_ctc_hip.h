@@ -139,6 +139,36 @@ size_t lc_xent_workspace_bytes(int T, int B, int V);
 int lc_xent_loss(const float *logits, int T, int B, int V, const int *targets, const int *seq_len, float *loss,
                  int *frames, int *correct, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream);
 
+/* Teacher-student distillation: per-frame KL divergence from a teacher's whole posterior to the student's, the soft-target
+ * relative of lc_xent_loss.  No reference counterpart.
+ *   logits  [T,B,V] time-major fp32, the student, as lc_xent_loss takes them;
+ *   teacher [T,B,V] teacher scores in the LOG domain (logits or log-posteriors: a per-row constant shift is immaterial;
+ *           -inf = probability 0);  seq_len [B];  teacher_len [B]: frames of utterance b that carry a teacher row.
+ * A frame (t, b) is SCORED when t < seq_len[b] and t < teacher_len[b].  With p = softmax(teacher / tau) and q =
+ * softmax(logits / tau), tau = temperature > 0:
+ *   loss [B]     sum over scored frames of KL(p || q) = sum_k p_k (log p_k - log q_k), natural log, p_k = 0 -> term 0;
+ *                NOT scaled by grad_scale and NOT clamped (a KL that rounds below zero stays there);
+ *   frames [B]   number of scored frames;
+ *   agree [B]    scored frames whose two argmaxes coincide (lowest index among equal maxima on both rows);
+ *   grad [T,B,V] or NULL: grad_scale * (q - p) on scored rows.  accumulate == 0: stored, every other row +0; accumulate != 0:
+ *                added to what grad holds, every other row left bit-exactly as it was (neither read nor written).
+ * The caller passes grad_scale = lambda * tau: the derivative of lambda * tau^2 * KL with respect to the logits.
+ * A teacher row whose maximum is not finite (all -inf, a +inf) or that holds a NaN makes loss[b] NaN; its frame counts
+ * nowhere and adds nothing to grad (a zero row when storing).  A student -inf where p_k > 0 gives +inf loss and a finite
+ * gradient row; student rows that are not finite behave as in lc_xent_loss.  An unscored frame's two rows are never read.
+ * Every element of loss, frames and agree (and of grad when storing) is written on every call; results are bit-identical
+ * from call to call and with and without a gradient (no atomics: 8 bytes per frame go to the workspace and a second launch
+ * folds each utterance's terms in a fixed order in double, rounding once).  Arithmetic per frame, fp32: both maxima are
+ * taken out first (a = s - max s, b = z - max z), then KL = sum_{p_k > 0} exp(a_k / tau) (a_k - b_k) / (tau Sp) + ln Sq - ln Sp
+ * with Sp, Sq the two sums of exponentials - no per-element log.  Rows of V <= 1024 are read once and kept in registers up
+ * to the gradient store (V <= 64: four frames per wave); wider rows are re-read.  T, B <= 0, V < 2, a temperature that is not
+ * finite and > 0, or a NULL required pointer: LC_EINVAL with no launch; a workspace below lc_kd_workspace_bytes:
+ * LC_EWORKSPACE; both leave every output alone.  Elements are indexed in 64 bits (T * B * V may exceed 2^31). */
+size_t lc_kd_workspace_bytes(int T, int B, int V);
+int lc_kd_loss(const float *logits, const float *teacher, int T, int B, int V, const int *seq_len, const int *teacher_len,
+               float temperature, float grad_scale, float *loss, int *frames, int *agree, float *grad, int accumulate,
+               void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* tf.edit_distance(hyp, truth, normalize=False) — nnet/graph.py:143-149.  HOST function on HOST
  * buffers (integer DP on a few hundred tokens; SURVEY.md §2a keeps it on the host). */
 int lc_edit_distance_host(const int *hyp, int hyp_stride, const int *hyp_len, const int *truth,

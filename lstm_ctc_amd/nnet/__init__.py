@@ -11,7 +11,8 @@ from .tfrecord import dataset_from_tfrecords, write_tfrecord
 
 __all__ = ["parse_config", "get_class_prior", "train", "validate", "create_graph_for_inference",
            "create_graph_for_training_ctc", "create_graph_for_validation_ctc", "create_graph_for_alignment",
-           "create_graph_for_training_xent", "create_graph_for_validation_xent", "Session",
+           "create_graph_for_training_xent", "create_graph_for_validation_xent", "create_graph_for_training_kd",
+           "create_graph_for_validation_kd", "Session",
            "get_create_logits", "create_logits_blstm", "create_logits_lstm", "create_logits_cudnnlstm",
            "create_pipeline_sequence_batch", "create_pipeline_sequential", "dataset_from_tfrecords",
            "write_tfrecord"]
@@ -23,6 +24,7 @@ def __getattr__(name):
         return getattr(funcs, name)
     if name in ("create_graph_for_inference", "create_graph_for_training_ctc", "create_graph_for_validation_ctc",
                 "create_graph_for_alignment", "create_graph_for_training_xent", "create_graph_for_validation_xent",
+                "create_graph_for_training_kd", "create_graph_for_validation_kd",
                 "Session", "OutOfRangeError", "get_create_logits", "create_logits_blstm", "create_logits_lstm",
                 "create_logits_cudnnlstm"):
         from . import graph

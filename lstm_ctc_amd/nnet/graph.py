@@ -144,16 +144,40 @@ class CTCGraph:
     over the paths that keep every label within N frames of the run ``batch["frame_target"]`` gives it
     (``ops.label_windows`` on the host, ``ops.ctc_loss_windowed`` where the step calls ``ops.ctc_loss``); an utterance whose
     row is all -1 or does not spell its labels trains on plain CTC.  ``windows_constrained`` / ``windows_unconstrained``
-    count the utterances of either kind.  ``None`` is the unwindowed step, untouched."""
+    count the utterances of either kind.  ``None`` is the unwindowed step, untouched.
+
+    ``teacher_weight=lambda`` (new, ``objective`` "ctc" or "xent"; a finite float > 0) adds teacher-student distillation to the
+    criterion: ``lambda * tau^2 * sum KL(softmax(teacher / tau) || softmax(logits / tau))`` over the frames that
+    ``batch["teacher_scores"]`` [T,B,V] / ``batch["teacher_length"]`` [B] cover, tau = ``teacher_temperature``
+    (``ops.kd_loss`` accumulating into the base criterion's gradient).  ``loss`` gains the term; ``eval_loss``, ``eval`` and
+    ``size`` stay the base criterion's; the output gains ``kd_loss`` (the plain sum of KL), ``kd_frames`` and ``kd_agree``.
+    ``objective="kd"`` is the term alone (lambda = 1): ``size`` is the number of scored frames, ``eval_loss`` = tau^2 * sum
+    KL, ``eval`` the frames whose two argmaxes disagree, and ``nnet_target`` is not read.  ``kd_frames_total`` /
+    ``kd_agree_total`` sum over the steps.  ``None`` is the step without the term, untouched."""
 
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
-                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None):
+                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None,
+                 teacher_weight=None, teacher_temperature=1.0):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
-        if objective not in ("ctc", "xent"):
+        if objective not in ("ctc", "xent", "kd"):
             raise ValueError("unsupported objective: %s" % objective)
         self.objective = objective
+        if teacher_weight is not None:
+            if objective == "kd":
+                raise ValueError("objective=\"kd\" is the distillation term alone (weight 1): it takes no teacher_weight")
+            if (isinstance(teacher_weight, bool) or not isinstance(teacher_weight, (int, float, np.integer, np.floating))
+                    or not np.isfinite(teacher_weight) or not teacher_weight > 0):
+                raise ValueError("teacher_weight must be a finite float > 0 or None, got %r" % (teacher_weight,))
+            teacher_weight = float(teacher_weight)
+        if (isinstance(teacher_temperature, bool) or not isinstance(teacher_temperature, (int, float, np.integer, np.floating))
+                or not np.isfinite(teacher_temperature) or not teacher_temperature > 0):
+            raise ValueError("teacher_temperature must be finite and > 0, got %r" % (teacher_temperature,))
+        self.teacher_weight = teacher_weight
+        self.teacher_temperature = float(teacher_temperature)
+        self.needs_teacher = objective == "kd" or teacher_weight is not None
+        self.kd_frames_total = self.kd_agree_total = 0
         if align_window is not None:
             if objective != "ctc":
                 raise ValueError("align_window constrains the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
@@ -231,6 +255,17 @@ class CTCGraph:
         ft = np.ascontiguousarray(batch["frame_target"], dtype=np.int32)
         return torch.from_numpy(ft).to(self.model.device, non_blocking=True), ft
 
+    def _upload_teacher(self, batch):
+        """teacher_weight / objective = kd: (teacher [T,B,V] f32, teacher_length [B] i32) on the device, (None, None) when the
+        batch carries none (``step`` raises for that).  Pure copies."""
+        ts = batch.get("teacher_scores")
+        if ts is None or batch.get("teacher_length") is None:
+            return None, None
+        dev = self.model.device
+        ts = np.ascontiguousarray(ts, dtype=np.float32)
+        tl = np.ascontiguousarray(batch["teacher_length"], dtype=np.int32)
+        return torch.from_numpy(ts).to(dev, non_blocking=True), torch.from_numpy(tl).to(dev, non_blocking=True)
+
     def _upload_windows(self, batch, flat, offs, seq):
         """align_window: (win_lo, win_hi on the device, constrained [B] on the host) from ``batch["frame_target"]``; (None,
         None, None) when the batch carries none (``step`` raises for that).  A pure function of the batch plus copies:
@@ -290,6 +325,8 @@ class CTCGraph:
                 up = up + self._upload_frame_target(batch)
             elif self.align_window is not None:
                 up = up + self._upload_windows(batch, up[5], up[6], up[2])
+            if self.needs_teacher:
+                up = up + self._upload_teacher(batch)
             ev = torch.cuda.Event()
             ev.record()
         return up, ev
@@ -311,11 +348,21 @@ class CTCGraph:
                 up = up + self._upload_frame_target(batch)
             elif self.align_window is not None:
                 up = up + self._upload_windows(batch, up[5], up[6], up[2])
+            if self.needs_teacher:
+                up = up + self._upload_teacher(batch)
+        teacher = None
+        if self.needs_teacher:
+            up, teacher = up[:-2], up[-2:]
+            if teacher[0] is None:
+                raise ValueError("teacher_weight / objective = kd needs teacher_scores and teacher_length in the batch "
+                                 "(create_pipeline_sequence_batch(..., teacher_scores=...))")
         x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = up[:8]
         ft_d = windows = None
         if self.objective == "xent":                  # reads no nnet_target: has_label = 0 corpora are fine
             ft_d, ft = up[8:]
             self._validate_frame_targets(ft, seq)
+        elif self.objective == "kd":                  # neither
+            pass
         else:
             self._validate_labels(flat)
             if self.align_window is not None:
@@ -328,17 +375,18 @@ class CTCGraph:
                 self.windows_unconstrained += int(len(constrained) - constrained.sum())
         out = self.step_device(x, seq_d, flat_d, offs_d, maxlen, int(len(flat)), fetch_eval=fetch_eval,
                                fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs, seq_host=seq,
-                               frame_target=ft_d, windows=windows)
+                               frame_target=ft_d, windows=windows, teacher=teacher)
         out["sequence_length"] = seq
         return out
 
     def step_device(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval=False, fetch_logits=False, train=None,
-                    flat_host=None, offs_host=None, seq_host=None, frame_target=None, windows=None):
+                    flat_host=None, offs_host=None, seq_host=None, frame_target=None, windows=None, teacher=None):
         """The same step on tensors already resident in HBM: x [T,B,D] time-major f32, seq_d [B] i32,
         labels flat i32 + offsets [B+1] i32.  seq_host: seq_d's values on the host, when the caller has them (pack_frames
         then builds a new batch's frame map without a device-to-host copy).  frame_target: [B,T] i32 on the device, the
         targets of objective = xent (labels / offsets / size are then not used).  windows: (win_lo, win_hi) int32 on the device,
-        parallel to the labels - required when the graph was built with align_window.
+        parallel to the labels - required when the graph was built with align_window.  teacher: (scores [T,B,V] f32 in the
+        log domain, teacher_length [B] i32) on the device - required with teacher_weight and under objective = kd.
 
         A persistent-recurrence launch that cannot complete (lstm_ctc_hip.h: bounded waits, sticky status word) leaves
         NaN outputs and makes the optimizer skip its update on the device; the word is read at the step's one sync
@@ -348,8 +396,11 @@ class CTCGraph:
         if self.align_window is not None and windows is None:
             raise ValueError("align_window needs the label windows (step: frame_target in the batch, frame_targets= of the "
                              "pipeline; step_device: windows=)")
+        if self.needs_teacher and (teacher is None or teacher[0] is None):
+            raise ValueError("teacher_weight / objective = kd needs the teacher scores (step: teacher_scores in the batch, "
+                             "teacher_scores= of the pipeline; step_device: teacher=)")
         args = (x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host, seq_host,
-                frame_target, windows)
+                frame_target, windows, teacher)
         if self._fallback.latched:                     # co-residency is structurally unavailable: stay on the train
             with ops.force_launch_train():
                 out, status = self._step_once(*args)
@@ -370,14 +421,16 @@ class CTCGraph:
         return out
 
     def _step_once(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
-                   seq_host=None, frame_target=None, windows=None):
+                   seq_host=None, frame_target=None, windows=None, teacher=None):
         dev = self.model.device
         ops.lstm_status(dev).zero_()
         self.global_step += 1
         self.drop_seed = (self.drop_seed * 1664525 + 1013904223) & 0x7FFFFFFF
         logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed, seq_len_host=seq_host)      # [T,B,V]
         if self.objective == "xent":
-            return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train)
+            return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train, teacher)
+        if self.objective == "kd":
+            return self._finish_kd(logits, seq_d, teacher, fetch_eval, fetch_logits, train)
         if self.align_window is not None:
             loss_b, grad = ops.ctc_loss_windowed(logits, flat_d, offs_d, seq_d, maxlen, windows[0], windows[1],
                                                  want_grad=train)
@@ -390,6 +443,7 @@ class CTCGraph:
             T_, B_, V_ = logits.shape
             reg = ops.label_smoothing(logits.view(T_ * B_, V_), self.sm_weight, self.sm_logq,
                                       grad.view(T_ * B_, V_) if train else None)
+        kd = self._teacher_term(logits, seq_d, teacher, grad, train)
         if fetch_eval:
             tokens, out_len = ops.ctc_greedy(logits, seq_d)
         bn_saved = None
@@ -400,7 +454,11 @@ class CTCGraph:
             self.model.backward(grad, buckets=self._buckets)
             self._apply_gradients()
         # one device->host sync per step, like the reference's sess.run
-        eval_loss = float(loss_b.sum().item())                                   # graph.py:116 reduce_sum
+        if kd is None:
+            eval_loss = float(loss_b.sum().item())                               # graph.py:116 reduce_sum
+        else:                                             # the same float32 sum, with the term's three scalars in its copy
+            word = torch.cat([loss_b.sum().to(torch.float64).view(1)] + self._kd_scalars(kd)).cpu().numpy()
+            eval_loss = float(word[0])
         status = int(ops.lstm_status(dev).item())
         if status != 0:
             return None, status
@@ -408,6 +466,8 @@ class CTCGraph:
             self.model.update_moving_averages(bn_saved)   # batch-norm UPDATE_OPS (graph.py:194-196); only with use_bn
         out["eval_loss"] = eval_loss
         out["loss"] = eval_loss + (float(reg.item()) if reg is not None else 0.0)
+        if kd is not None:
+            out["loss"] += self._kd_outputs(out, word[1:4])
         if fetch_eval:
             tok, n = tokens.cpu().numpy(), out_len.cpu().numpy()
             if flat_host is None:
@@ -420,14 +480,35 @@ class CTCGraph:
             out["grad_norm"] = float(self.norm_out[0].item())
         return out, 0
 
-    def _finish_xent(self, logits, seq_d, frame_target, fetch_eval, fetch_logits, train):
-        """The rest of a step under objective = xent: ``ops.xent_loss`` in the place of ``ops.ctc_loss``; regulariser,
-        backward, L2, clip, optimizer and status word as in the CTC step.  A batch without a scored frame (size 0) still
-        runs the optimizer step - on a zero loss gradient - so that ranks stay in lockstep."""
-        if frame_target is None:
-            raise ValueError("objective = xent needs frame_target (create_pipeline_sequence_batch(..., frame_targets=...))")
+    def _teacher_term(self, logits, seq_d, teacher, grad, train):
+        """teacher_weight on a base criterion: ``ops.kd_loss`` adding lambda * tau * (q - p) to the criterion's gradient
+        (loss only when not training).  None without the option."""
+        if self.teacher_weight is None:
+            return None
+        tau = self.teacher_temperature
+        return ops.kd_loss(logits, teacher[0], seq_d, teacher[1], temperature=tau, grad_scale=self.teacher_weight * tau,
+                           grad=grad if train else None, want_grad=False)[:3]
+
+    @staticmethod
+    def _kd_scalars(kd):
+        return [t.to(torch.float64).sum().view(1) for t in kd]
+
+    def _kd_outputs(self, out, word):
+        """Writes kd_loss / kd_frames / kd_agree into ``out`` and returns what the term adds to ``loss``."""
+        tau = self.teacher_temperature
+        out["kd_loss"], out["kd_frames"], out["kd_agree"] = float(word[0]), int(word[1]), int(word[2])
+        self.kd_frames_total += out["kd_frames"]
+        self.kd_agree_total += out["kd_agree"]
+        return (1.0 if self.teacher_weight is None else self.teacher_weight) * tau * tau * out["kd_loss"]
+
+    def _finish_kd(self, logits, seq_d, teacher, fetch_eval, fetch_logits, train):
+        """The rest of a step under objective = kd: ``ops.kd_loss`` in the place of ``ops.ctc_loss`` (lambda = 1);
+        regulariser, backward, L2, clip, optimizer and status word as in the CTC step.  A batch without a scored frame (size
+        0) still runs the optimizer step - on a zero loss gradient - so that ranks stay in lockstep."""
         dev = self.model.device
-        loss_b, frames, correct, grad = ops.xent_loss(logits, frame_target, seq_d, want_grad=train)
+        tau = self.teacher_temperature
+        loss_b, frames, agree, grad = ops.kd_loss(logits, teacher[0], seq_d, teacher[1], temperature=tau, grad_scale=tau,
+                                                  want_grad=train)
         reg = None
         if self.sm_weight > 0:
             T_, B_, V_ = logits.shape
@@ -441,11 +522,55 @@ class CTCGraph:
             self.model.backward(grad, buckets=self._buckets)
             self._apply_gradients()
         # everything the host wants, in ONE device->host copy: the step's single sync
+        zero = torch.zeros(1, dtype=torch.float64, device=dev)
+        word = torch.cat(self._kd_scalars((loss_b, frames, agree, ops.lstm_status(dev))) +
+                         [reg.to(torch.float64).view(1) if reg is not None else zero,
+                          self.norm_out[:1].to(torch.float64) if train else zero]).cpu().numpy()
+        status = int(word[3])
+        if status != 0:
+            return None, status
+        if train and bn_saved:
+            self.model.update_moving_averages(bn_saved)
+        out = {}
+        out["eval_loss"] = self._kd_outputs(out, word[:3])
+        out["size"] = out["kd_frames"]
+        out["loss"] = out["eval_loss"] + float(word[4])
+        if fetch_eval:
+            out["eval"] = float(out["kd_frames"] - out["kd_agree"])      # frames whose two argmaxes disagree
+        if fetch_logits:
+            out["logits"] = logits.permute(1, 0, 2).cpu().numpy()
+        if train:
+            out["grad_norm"] = float(word[5])
+        return out, 0
+
+    def _finish_xent(self, logits, seq_d, frame_target, fetch_eval, fetch_logits, train, teacher=None):
+        """The rest of a step under objective = xent: ``ops.xent_loss`` in the place of ``ops.ctc_loss``; regulariser,
+        backward, L2, clip, optimizer and status word as in the CTC step.  A batch without a scored frame (size 0) still
+        runs the optimizer step - on a zero loss gradient - so that ranks stay in lockstep."""
+        if frame_target is None:
+            raise ValueError("objective = xent needs frame_target (create_pipeline_sequence_batch(..., frame_targets=...))")
+        dev = self.model.device
+        loss_b, frames, correct, grad = ops.xent_loss(logits, frame_target, seq_d, want_grad=train)
+        reg = None
+        if self.sm_weight > 0:
+            T_, B_, V_ = logits.shape
+            reg = ops.label_smoothing(logits.view(T_ * B_, V_), self.sm_weight, self.sm_logq,
+                                      grad.view(T_ * B_, V_) if train else None)
+        kd = self._teacher_term(logits, seq_d, teacher, grad, train)
+        bn_saved = None
+        if train:
+            bn_saved = dict(self.model.saved.get("bn") or {})
+            self._buckets = (dp.GradientBuckets(self.model.ps.grad, self.pg)
+                             if self.pg is not None and self.dp_buckets and (self.world > 1 or self._force_buckets) else None)
+            self.model.backward(grad, buckets=self._buckets)
+            self._apply_gradients()
+        # everything the host wants, in ONE device->host copy: the step's single sync
         f64 = lambda t: t.to(torch.float64).sum().view(1)
         zero = torch.zeros(1, dtype=torch.float64, device=dev)
         word = torch.cat([f64(loss_b), f64(frames), f64(correct), f64(ops.lstm_status(dev)),
                           reg.to(torch.float64).view(1) if reg is not None else zero,
-                          self.norm_out[:1].to(torch.float64) if train else zero]).cpu().numpy()
+                          self.norm_out[:1].to(torch.float64) if train else zero] +
+                         (self._kd_scalars(kd) if kd is not None else [])).cpu().numpy()
         status = int(word[3])
         if status != 0:
             return None, status
@@ -453,6 +578,8 @@ class CTCGraph:
             self.model.update_moving_averages(bn_saved)
         n_frames = int(word[1])
         out = {"size": n_frames, "eval_loss": float(word[0]), "loss": float(word[0]) + float(word[4])}
+        if kd is not None:
+            out["loss"] += self._kd_outputs(out, word[6:9])
         if fetch_eval:
             out["eval"] = float(n_frames - int(word[2]))          # frames the argmax gets wrong
         if fetch_logits:
@@ -608,27 +735,46 @@ def load_params(ps, path):
 
 
 # ----------------------------------------------------------------------------------------------------- reference-named factories
-def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None, align_window=None):
-    return CTCGraph(pipeline, nnet_config, device=device, seed=seed, align_window=align_window)
+def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None, align_window=None,
+                                    teacher_weight=None, teacher_temperature=1.0):
+    return CTCGraph(pipeline, nnet_config, device=device, seed=seed, align_window=align_window,
+                    teacher_weight=teacher_weight, teacher_temperature=teacher_temperature)
 
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
-                                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None):
+                                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None,
+                                  teacher_weight=None, teacher_temperature=1.0):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
-                    align_window=align_window)
+                    align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature)
 
 
-def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None):
+def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None, teacher_weight=None,
+                                     teacher_temperature=1.0):
     """Frame cross-entropy against the pipeline's ``frame_target`` (new, no reference counterpart)."""
-    return CTCGraph(pipeline, nnet_config, device=device, seed=seed, objective="xent")
+    return CTCGraph(pipeline, nnet_config, device=device, seed=seed, objective="xent", teacher_weight=teacher_weight,
+                    teacher_temperature=teacher_temperature)
 
 
 def create_graph_for_training_xent(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
-                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None):
+                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, teacher_weight=None,
+                                   teacher_temperature=1.0):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
-                    objective="xent")
+                    objective="xent", teacher_weight=teacher_weight, teacher_temperature=teacher_temperature)
+
+
+def create_graph_for_validation_kd(pipeline, nnet_config, device="cuda", seed=None, teacher_temperature=1.0):
+    """Distillation alone against the pipeline's ``teacher_scores`` (new, no reference counterpart)."""
+    return CTCGraph(pipeline, nnet_config, device=device, seed=seed, objective="kd",
+                    teacher_temperature=teacher_temperature)
+
+
+def create_graph_for_training_kd(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
+                                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, teacher_temperature=1.0):
+    return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
+                    l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
+                    objective="kd", teacher_temperature=teacher_temperature)
 
 
 def create_graph_for_alignment(pipeline, nnet_config, device="cuda"):

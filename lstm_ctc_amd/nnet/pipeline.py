@@ -78,8 +78,25 @@ class _HostBuffers:
 
 class SequenceBatchPipeline:
     def __init__(self, dataset, input_dim, batch_size, rank=0, world_size=1, prefetch=4, batch_threads=2,
-                 num_parallel_calls=None, frame_targets=None):
+                 num_parallel_calls=None, frame_targets=None, teacher_scores=None, teacher_domain="log", num_targets=None):
         self.dataset, self.input_dim, self.batch_size = dataset, input_dim, batch_size
+        # teacher scores (new, distillation): a table {utterance key: float matrix [frames, num_targets]} - a
+        # kaldi_io.FloatMatrixTable (read lazily, entry by entry, from the batch threads) or a dict of arrays - in the log
+        # domain (log-posteriors or logits) or, with teacher_domain = "prob", probabilities whose log is taken on read.
+        # Utterances without an entry, with an entry of another shape than [frames after splice / subsample, num_targets],
+        # or with a row whose maximum is not finite / any NaN are counted and get teacher_length 0.  num_targets = None takes
+        # the column count of the table's first entry.
+        if teacher_domain not in ("log", "prob"):
+            raise ValueError("teacher_domain must be \"log\" or \"prob\", got %r" % (teacher_domain,))
+        self.teacher_scores, self.teacher_domain = teacher_scores, teacher_domain
+        self.teacher_dim = None if num_targets is None else int(num_targets)
+        if teacher_scores is not None and self.teacher_dim is None:
+            for key in teacher_scores.keys():
+                self.teacher_dim = int(self._teacher_shape(key)[1])
+                break
+            else:
+                raise ValueError("teacher_scores is an empty table: pass num_targets")
+        self.teacher_missing = self.teacher_mismatched = self.teacher_bad = 0
         # frame-level targets (new, the xent objective): {utterance key: int32 vector, one symbol per frame}; the key is the
         # TFRecord file's basename without extension, what nnet-align / nnet-forward write.  Utterances without an entry, or
         # whose entry does not have the utterance's frame count (after splice / subsample), are counted and get no target.
@@ -115,6 +132,45 @@ class SequenceBatchPipeline:
             self.targets_mismatched += mismatched
         return out
 
+    def _teacher_shape(self, key):
+        table = self.teacher_scores
+        return table.shape(key) if hasattr(table, "shape") else np.shape(table[key])
+
+    def _teacher(self, paths, frames, T):
+        """``teacher_scores`` [T, B, V] float32 (time-major, contiguous; zeros in padding and for uncovered utterances) and
+        ``teacher_length`` [B] int32 (the utterance's frame count, or 0) of a batch.  The three kinds of uncovered utterance
+        are counted."""
+        table, V = self.teacher_scores, self.teacher_dim
+        out = np.zeros((T, len(paths), V), np.float32)
+        length = np.zeros(len(paths), np.int32)
+        missing = mismatched = bad = 0
+        for b, path in enumerate(paths):
+            key = self.utterance_key(path)
+            if key not in table:
+                missing += 1
+                continue
+            n = int(frames[b])
+            if tuple(self._teacher_shape(key)) != (n, V):
+                mismatched += 1
+                continue
+            m = np.asarray(table.get(key), np.float32)
+            if self.teacher_domain == "prob":
+                if (m < 0).any():                                  # a negative probability (a NaN is caught below)
+                    bad += 1
+                    continue
+                with np.errstate(divide="ignore"):
+                    m = np.log(m)
+            if n and not np.isfinite(m.max(axis=1)).all():         # a row's maximum: NaN if the row holds one, +-inf
+                bad += 1
+                continue
+            out[:n, b] = m
+            length[b] = n
+        with self._count_lock:
+            self.teacher_missing += missing
+            self.teacher_mismatched += mismatched
+            self.teacher_bad += bad
+        return out, length
+
     def _collate(self, items, paths=None):
         """Padding of already-loaded utterance dicts (any dataset with ``load``): the generic, copying form."""
         B = len(items)
@@ -133,6 +189,10 @@ class SequenceBatchPipeline:
             if paths is None:
                 raise ValueError("frame_targets need the utterances' paths (their keys)")
             batch["frame_target"] = self._frame_target(paths, batch["sequence_length"], T)
+        if self.teacher_scores is not None:
+            if paths is None:
+                raise ValueError("teacher_scores need the utterances' paths (their keys)")
+            batch["teacher_scores"], batch["teacher_length"] = self._teacher(paths, batch["sequence_length"], T)
         return batch
 
     def _assemble(self, paths, pool, buffers):
@@ -152,6 +212,8 @@ class SequenceBatchPipeline:
                  "sequence_length": nb.frames.copy(), "target_length": nb.labels.copy()}
         if self.frame_targets is not None:
             batch["frame_target"] = self._frame_target(paths, nb.frames, T)
+        if self.teacher_scores is not None:
+            batch["teacher_scores"], batch["teacher_length"] = self._teacher(paths, nb.frames, T)
         return batch
 
     def _starts(self):
@@ -211,12 +273,17 @@ class SequenceBatchPipeline:
 
 
 def create_pipeline_sequence_batch(dataset, input_dim, batch_size=64, batch_threads=8, num_epochs=1, rank=0,
-                                   world_size=1, num_parallel_calls=None, frame_targets=None):
+                                   world_size=1, num_parallel_calls=None, frame_targets=None, teacher_scores=None,
+                                   teacher_domain="log", num_targets=None):
     """Returns (initializer, pipeline) like the reference; the initializer is a no-op callable.  ``frame_targets`` (new):
-    {utterance key: int32 vector}; every batch then carries ``frame_target`` [B, T] int32 padded with -1."""
+    {utterance key: int32 vector}; every batch then carries ``frame_target`` [B, T] int32 padded with -1.
+    ``teacher_scores`` (new): a table {utterance key: float matrix [frames, num_targets]} (``kaldi_io.FloatMatrixTable`` or
+    a dict) in the ``teacher_domain`` "log" or "prob"; every batch then carries ``teacher_scores`` [T, B, V] float32 in the log
+    domain and ``teacher_length`` [B] int32 (0 for an utterance the table does not cover)."""
     return (lambda: None), SequenceBatchPipeline(dataset, input_dim, batch_size, rank, world_size,
                                                  batch_threads=batch_threads, num_parallel_calls=num_parallel_calls,
-                                                 frame_targets=frame_targets)
+                                                 frame_targets=frame_targets, teacher_scores=teacher_scores,
+                                                 teacher_domain=teacher_domain, num_targets=num_targets)
 
 
 class SequentialPipeline:

@@ -396,6 +396,43 @@ def xent_loss(logits, targets, seq_len, want_grad=True):
     return loss, frames, correct, grad
 
 
+def kd_loss(logits, teacher, seq_len, teacher_len, temperature=1.0, grad_scale=1.0, grad=None, want_grad=True):
+    """Teacher-student distillation - no reference counterpart.  logits, teacher [T,B,V] f32 (teacher in the log domain;
+    -inf = probability 0); seq_len, teacher_len [B] int32.  A frame is scored when t < min(seq_len[b], teacher_len[b]).
+    Returns (loss [B] f32, frames [B] int32, agree [B] int32, grad) on the device: the summed KL(softmax(teacher / tau) ||
+    softmax(logits / tau)) of the scored frames (not scaled), their number, how many of them have the two argmaxes
+    coincide, and grad_scale * (q - p).  ``grad=None`` allocates a tensor and overwrites it (zero rows on frames that are
+    not scored); a given tensor is accumulated into (rows that are not scored stay untouched); ``want_grad=False`` with
+    ``grad=None`` computes no gradient and returns None."""
+    lib = _lib.load()
+    _require_cuda(logits, teacher, seq_len, teacher_len, grad)
+    logits = _f32c(logits)
+    teacher = _f32c(teacher)
+    T, B, V = logits.shape
+    assert seq_len.dtype == torch.int32 and teacher_len.dtype == torch.int32
+    if tuple(teacher.shape) != (T, B, V) or seq_len.numel() != B or teacher_len.numel() != B:
+        raise ValueError("kd_loss: teacher must be [T, B, V] = [%d, %d, %d], seq_len and teacher_len [B] (got %s, %s, %s)"
+                         % (T, B, V, tuple(teacher.shape), tuple(seq_len.shape), tuple(teacher_len.shape)))
+    accumulate = grad is not None
+    if accumulate:
+        if grad.dtype != torch.float32 or tuple(grad.shape) != (T, B, V) or not grad.is_contiguous():
+            raise ValueError("kd_loss: grad must be a contiguous float32 [T, B, V] tensor to accumulate into")
+    elif want_grad:
+        grad = torch.empty_like(logits)
+    dev = logits.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    agree = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.lc_kd_workspace_bytes(T, B, V)
+    ws = workspace("kd", nbytes, dev)
+    ev = _prof_begin()
+    _lib.check(lib.lc_kd_loss(_ptr(logits), _ptr(teacher), T, B, V, _ptr(seq_len.contiguous()), _ptr(teacher_len.contiguous()),
+                              float(temperature), float(grad_scale), _ptr(loss), _ptr(frames), _ptr(agree), _ptr(grad),
+                              1 if accumulate else 0, _ptr(ws), nbytes, _stream()), "lc_kd_loss")
+    _prof_end("kd", (T, B, V), ev)
+    return loss, frames, agree, grad
+
+
 def alignment_segments(ali, label_index, seq_len):
     """HOST function on numpy arrays: ali / label_index [B,T] and seq_len [B] as :func:`ctc_align` returns them ->
     per utterance a list of (label, start_frame, num_frames) runs of non-blank frames.  A run ends where label_index
