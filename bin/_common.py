@@ -164,6 +164,29 @@ def report_label_windows(graph):
                % (graph.align_window, graph.windows_constrained, graph.windows_unconstrained))
 
 
+def delay_keywords(args):
+    """--delay-penalty: the graph keyword, empty without the flag (nnet-init has none).  The FATAL line and exit 1 when the
+    value is negative or not finite, or meets another objective than ctc.  Host work only: runs BEFORE the device is set up."""
+    penalty = getattr(args, 'delay_penalty', None)
+    if penalty is None:
+        return {}
+    import math
+    if not (math.isfinite(penalty) and penalty >= 0):
+        _fatal('--delay-penalty must be a finite number >= 0, got %r' % penalty)
+    if args.objective != 'ctc':
+        _fatal('--delay-penalty tilts the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
+    return {'delay_penalty': penalty}
+
+
+def report_delay_penalty(graph):
+    """One INFO line at the end of a pass under --delay-penalty: the mean frame at which a label is entered, under the
+    criterion's own path posterior."""
+    from lstm_ctc_amd.nnet import tflog
+    n = graph.entry_labels_total
+    tflog.info('delay penalty %g: mean label entry frame %.3f over %d label(s)'
+               % (graph.delay_penalty, graph.entry_sum_total / max(n, 1), n))
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:
@@ -198,6 +221,9 @@ FLAGS = {
     '--align-window': dict(type=int, default=None, help='with --objective ctc and --frame-targets: sum the CTC criterion only over '
                            'paths that keep every label within this many frames of where the alignment table puts it (new); '
                            'utterances the table does not cover train on plain CTC'),
+    '--delay-penalty': dict(type=float, default=None, help='with --objective ctc: weight every path by exp(-penalty * sum of the '
+                            'frames at which its labels are entered), so that the model learns to emit earlier (new); needs no '
+                            'table, composes with --align-window; 0 is plain CTC and reports the mean label entry frame'),
     '--optimizer': dict(type=str, default='sgd', help='sgd | momentum (0.9) | adam, constant learning rate'),
     '--evaluate': dict(type=str2bool, default='false', help='also report an error rate: greedy decoding and the token error rate (ctc), the frame error rate (xent)'),
     '--learn-rate': dict(type=float, default=0.0001, help='step size of the optimizer'),

@@ -116,6 +116,31 @@ int lc_ctc_loss_windowed(const float *logits, int T, int B, int V, const int *la
                          const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
                          float *loss, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream);
 
+/* Delay-penalised CTC (Kang et al. 2023): the CTC criterion over paths weighted by exp(-delay_penalty * E(path)), E(path) =
+ * sum over the labels of the first frame of the label's run - "emit earlier" without an alignment - and the expectation of E
+ * under that weighted path posterior.  No reference counterpart.  Everything not said here is lc_ctc_loss_windowed's contract.
+ *   win_lo, win_hi  both NULL = unconstrained; else lc_ctc_loss_windowed's windows (exactly one NULL is LC_EINVAL);
+ *   delay_penalty   lambda, any finite value (not finite -> LC_EINVAL); 0 is plain (windowed) CTC.  The weight sits on the
+ *                   ARCS that enter a label position (from s-1 or s-2) at frame t, exp(-lambda * t), not centred: frame 0
+ *                   carries none, "stay" arcs and arcs into blanks carry none, so loss >= the unpenalised loss for lambda >= 0;
+ *   loss [B]        -log sum_path p(path | x) exp(-lambda E(path)), natural log;
+ *   entry_sum [B]   or NULL: E_q[E(path)], q(path) ~ p(path | x) exp(-lambda E(path)) = d loss / d lambda = sum_t sum_s
+ *                   occupancy(t, s) * (L - (s + 1) / 2).  entry_sum / L is the mean frame at which a label is entered;
+ *   grad [T,B,V]    or NULL: softmax - occupancy under q on live frames, +0 for t >= seq_len[b].
+ * lc_ctc_loss's conventions: a skipped utterance -> loss 0, entry_sum 0, gradient 0; a bad label -> loss NaN, entry_sum NaN,
+ * gradient 0; no surviving path -> loss +inf, entry_sum 0, gradient = softmax, no NaN anywhere; L = 0 -> the all-blank path
+ * (entry_sum 0).  Every element of every output is written on every call; results are bit-identical from call to call and
+ * loss is bit-identical whichever of entry_sum / grad are NULL (no atomics, fixed summation orders).  A non-NULL entry_sum
+ * runs both sweeps also without a gradient.  Arithmetic: lc_ctc_loss_windowed's (fp32 log-softmax emissions, double cells
+ * in the log2 domain); the arc weight -lambda * log2(e) * t is formed and added in double; log p, the occupancy exponents and
+ * entry_sum (per-frame terms in the workspace, folded per utterance in a fixed order) are formed in double and rounded once.
+ * Shapes and errors as for lc_ctc_loss_windowed; the workspace holds T * B doubles more. */
+size_t lc_ctc_delay_workspace_bytes(int T, int B, int V, int max_label_len);
+int lc_ctc_loss_delay(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                      const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi, float delay_penalty,
+                      float *loss, float *entry_sum, float *grad, void *workspace, size_t workspace_bytes,
+                      lc_stream_t stream);
+
 /* Frame-level softmax cross-entropy against one target symbol per frame - the objective that trains on what lc_ctc_align
  * writes.  No reference counterpart (the reference never finished frame-level training).
  *   logits [T,B,V] time-major fp32; targets [B,T] int32 (the layout of lc_ctc_align's ali); seq_len [B].

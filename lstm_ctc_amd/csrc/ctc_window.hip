@@ -33,6 +33,7 @@
 //      lane by lane and then by the wave's DPP reduction.  grad = softmax - occupancy.
 // The band (only positions whose window contains t are live) is NOT exploited: every position is computed on every frame.
 #include "common.h"
+#include "ctc_lattice.h"
 #include <float.h>
 #include <limits.h>
 #include <math.h>
@@ -102,33 +103,7 @@ __global__ __launch_bounds__(256) void cw_index_kernel(int V, const int *__restr
 }
 
 // ------------------------------------------------------------------------------------------ 3. alpha / beta sweeps
-__device__ __forceinline__ double cw_neg_inf() { return __longlong_as_double(0xfff0000000000000ull); }
-// log2(2^a + 2^b [+ 2^c]); -inf operands are "log zero", all of them -inf gives -inf (see the header)
-__device__ __forceinline__ double cw_lse2(double a, double b)
-{
-    const double m = fmax(fmax(a, b), -DBL_MAX);
-    return m + (double)__builtin_amdgcn_logf(__builtin_amdgcn_exp2f((float)(a - m)) + __builtin_amdgcn_exp2f((float)(b - m)));
-}
-__device__ __forceinline__ double cw_lse3(double a, double b, double c)
-{
-    const double m = fmax(fmax(fmax(a, b), c), -DBL_MAX);
-    return m + (double)__builtin_amdgcn_logf(__builtin_amdgcn_exp2f((float)(a - m)) + __builtin_amdgcn_exp2f((float)(b - m)) +
-                                             __builtin_amdgcn_exp2f((float)(c - m)));
-}
-// lane i receives x of lane i-1, lane 0 receives -inf (two 32-bit DPP wave_shr:1 moves)
-__device__ __forceinline__ double cw_shr1(double x)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)0xfff00000, __double2hiint(x), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double cw_readlane(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
+// cw_neg_inf / cw_lse2 / cw_lse3 / cw_shr1 / cw_readlane: ctc_lattice.h (shared with ctc_delay.hip)
 template <int PPL>
 __global__ __launch_bounds__(64) void cw_sweep_kernel(const float *__restrict__ logits, int T, int B, int V,
                                                       const int *__restrict__ labels, const int *__restrict__ offs,

@@ -153,11 +153,19 @@ class CTCGraph:
     ``size`` stay the base criterion's; the output gains ``kd_loss`` (the plain sum of KL), ``kd_frames`` and ``kd_agree``.
     ``objective="kd"`` is the term alone (lambda = 1): ``size`` is the number of scored frames, ``eval_loss`` = tau^2 * sum
     KL, ``eval`` the frames whose two argmaxes disagree, and ``nnet_target`` is not read.  ``kd_frames_total`` /
-    ``kd_agree_total`` sum over the steps.  ``None`` is the step without the term, untouched."""
+    ``kd_agree_total`` sum over the steps.  ``None`` is the step without the term, untouched.
+
+    ``delay_penalty=lambda`` (new, ``objective="ctc"`` only; a finite float >= 0) is delay-penalised CTC: a path is weighted
+    by ``exp(-lambda * sum of the frames at which its labels are entered)`` (``ops.ctc_loss_delay`` where the step calls
+    ``ops.ctc_loss`` / ``ops.ctc_loss_windowed``; with ``align_window`` the windows go to it).  ``eval_loss`` / ``loss`` are the
+    penalised criterion; the output gains ``entry_sum`` (the expected sum of the label entry frames under the criterion's
+    path posterior) and ``entry_labels`` (the labels of the utterances with a finite, non-skipped loss), so that
+    ``entry_sum / entry_labels`` is the mean frame at which a label is entered; ``entry_sum_total`` / ``entry_labels_total``
+    sum over the steps.  0 is plain CTC plus the metric.  ``None`` is the step without it, untouched."""
 
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None,
-                 teacher_weight=None, teacher_temperature=1.0):
+                 teacher_weight=None, teacher_temperature=1.0, delay_penalty=None):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
@@ -186,6 +194,15 @@ class CTCGraph:
             align_window = int(align_window)
         self.align_window = align_window
         self.windows_constrained = self.windows_unconstrained = 0
+        if delay_penalty is not None:
+            if objective != "ctc":
+                raise ValueError("delay_penalty tilts the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
+            if (isinstance(delay_penalty, bool) or not isinstance(delay_penalty, (int, float, np.integer, np.floating))
+                    or not np.isfinite(delay_penalty) or delay_penalty < 0):
+                raise ValueError("delay_penalty must be a finite float >= 0 or None, got %r" % (delay_penalty,))
+            delay_penalty = float(delay_penalty)
+        self.delay_penalty = delay_penalty
+        self.entry_sum_total, self.entry_labels_total = 0.0, 0
         self.pipeline = pipeline
         self.model = Model(nnet_config, device, seed=seed)
         self.training = learn_rate is not None
@@ -431,7 +448,12 @@ class CTCGraph:
             return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train, teacher)
         if self.objective == "kd":
             return self._finish_kd(logits, seq_d, teacher, fetch_eval, fetch_logits, train)
-        if self.align_window is not None:
+        entry_b = None
+        if self.delay_penalty is not None:
+            lo_d, hi_d = windows if self.align_window is not None else (None, None)
+            loss_b, entry_b, grad = ops.ctc_loss_delay(logits, flat_d, offs_d, seq_d, maxlen, self.delay_penalty, win_lo=lo_d,
+                                                       win_hi=hi_d, want_grad=train)
+        elif self.align_window is not None:
             loss_b, grad = ops.ctc_loss_windowed(logits, flat_d, offs_d, seq_d, maxlen, windows[0], windows[1],
                                                  want_grad=train)
         else:
@@ -454,10 +476,12 @@ class CTCGraph:
             self.model.backward(grad, buckets=self._buckets)
             self._apply_gradients()
         # one device->host sync per step, like the reference's sess.run
-        if kd is None:
+        if kd is None and entry_b is None:
             eval_loss = float(loss_b.sum().item())                               # graph.py:116 reduce_sum
-        else:                                             # the same float32 sum, with the term's three scalars in its copy
-            word = torch.cat([loss_b.sum().to(torch.float64).view(1)] + self._kd_scalars(kd)).cpu().numpy()
+        else:                                             # the same float32 sum, with the options' scalars in its copy
+            word = torch.cat([loss_b.sum().to(torch.float64).view(1)] + (self._kd_scalars(kd) if kd is not None else []) +
+                             (self._entry_scalars(loss_b, entry_b, offs_d, seq_d) if entry_b is not None else [])
+                             ).cpu().numpy()
             eval_loss = float(word[0])
         status = int(ops.lstm_status(dev).item())
         if status != 0:
@@ -468,6 +492,10 @@ class CTCGraph:
         out["loss"] = eval_loss + (float(reg.item()) if reg is not None else 0.0)
         if kd is not None:
             out["loss"] += self._kd_outputs(out, word[1:4])
+        if entry_b is not None:
+            out["entry_sum"], out["entry_labels"] = float(word[-2]), int(word[-1])
+            self.entry_sum_total += out["entry_sum"]
+            self.entry_labels_total += out["entry_labels"]
         if fetch_eval:
             tok, n = tokens.cpu().numpy(), out_len.cpu().numpy()
             if flat_host is None:
@@ -488,6 +516,15 @@ class CTCGraph:
         tau = self.teacher_temperature
         return ops.kd_loss(logits, teacher[0], seq_d, teacher[1], temperature=tau, grad_scale=self.teacher_weight * tau,
                            grad=grad if train else None, want_grad=False)[:3]
+
+    @staticmethod
+    def _entry_scalars(loss_b, entry_b, offs_d, seq_d):
+        """delay_penalty: [sum of entry_sum, number of labels] over the utterances with a finite, non-skipped loss."""
+        n = (offs_d[1:] - offs_d[:-1]).to(torch.int64)
+        ok = torch.isfinite(loss_b) & (seq_d > 0) & (n <= seq_d)
+        zero = torch.zeros((), dtype=torch.float64, device=loss_b.device)
+        return [torch.where(ok, entry_b.to(torch.float64), zero).sum().view(1),
+                torch.where(ok, n, torch.zeros_like(n)).sum().to(torch.float64).view(1)]
 
     @staticmethod
     def _kd_scalars(kd):
@@ -736,17 +773,18 @@ def load_params(ps, path):
 
 # ----------------------------------------------------------------------------------------------------- reference-named factories
 def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None, align_window=None,
-                                    teacher_weight=None, teacher_temperature=1.0):
+                                    teacher_weight=None, teacher_temperature=1.0, delay_penalty=None):
     return CTCGraph(pipeline, nnet_config, device=device, seed=seed, align_window=align_window,
-                    teacher_weight=teacher_weight, teacher_temperature=teacher_temperature)
+                    teacher_weight=teacher_weight, teacher_temperature=teacher_temperature, delay_penalty=delay_penalty)
 
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None,
-                                  teacher_weight=None, teacher_temperature=1.0):
+                                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
-                    align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature)
+                    align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature,
+                    delay_penalty=delay_penalty)
 
 
 def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None, teacher_weight=None,

@@ -298,6 +298,45 @@ def ctc_loss_windowed(logits, labels, offsets, seq_len, max_label_len, win_lo, w
     return loss, grad
 
 
+def ctc_loss_delay(logits, labels, offsets, seq_len, max_label_len, delay_penalty, win_lo=None, win_hi=None, want_grad=True,
+                   want_entry=True):
+    """Delay-penalised CTC - no reference counterpart.  Arguments as for :func:`ctc_loss`, plus delay_penalty (lambda, any
+    finite float: a path is weighted by exp(-lambda * sum of the frames at which its labels are entered)) and, optionally,
+    the windows of :func:`ctc_loss_windowed` (both or none).  Returns (loss[B], entry_sum[B] or None, grad[T,B,V] or None):
+    entry_sum is the expected sum of the label entry frames under the penalised path posterior, = d loss / d lambda."""
+    lib = _lib.load()
+    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
+    if isinstance(delay_penalty, bool) or not np.isfinite(delay_penalty):
+        raise ValueError("ctc_loss_delay: delay_penalty must be a finite float, got %r" % (delay_penalty,))
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError("ctc_loss_delay: win_lo and win_hi go together (both or none)")
+    if win_lo is not None:
+        assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
+        if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
+            raise ValueError("ctc_loss_delay: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
+                             % (win_lo.numel(), win_hi.numel(), labels.numel()))
+        win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    entry = torch.empty(B, dtype=torch.float32, device=logits.device) if want_entry else None
+    grad = torch.empty_like(logits) if want_grad else None
+    nbytes = lib.lc_ctc_delay_workspace_bytes(T, B, V, int(max_label_len))
+    ws = workspace("ctc_delay", nbytes, logits.device)
+    if labels.numel() == 0:
+        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
+        if win_lo is not None:
+            win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
+            win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    ev = _prof_begin()
+    _lib.check(lib.lc_ctc_loss_delay(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len),
+                                     _ptr(win_lo), _ptr(win_hi), float(delay_penalty), _ptr(loss), _ptr(entry), _ptr(grad),
+                                     _ptr(ws), nbytes, _stream()), "lc_ctc_loss_delay")
+    _prof_end("ctc", (T, B, V), ev)
+    return loss, entry, grad
+
+
 WINDOW_OPEN = np.iinfo(np.int32).max
 
 
