@@ -340,7 +340,8 @@ int lc_gemm_bf16x3_tn(int M, int N, int K, float alpha, const uint16_t *A, int l
  *   cs, hs [T,B,N]   out: cell state c_t and pre-projection output m'_t (0 where t >= seq_len[b])
  *   reverse != 0     run t = T-1..0: the reference's reverse_sequence -> dynamic_rnn -> reverse_sequence
  *                    (bilstm.py:112,180-190) done by index arithmetic.
- * Requires N % 8 == 0 (N % 16 == 0 for the backward). */
+ * Requires N % 16 == 0 in both passes of lc_lstm_fwd / lc_lstm_bwd and of the split-operand entry points, and
+ * N % 32 == 0 in both passes of the bf16 ones; anything else is refused with LC_EINVAL before any launch. */
 typedef struct {
     float *zx;
     const float *R;
