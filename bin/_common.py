@@ -187,6 +187,41 @@ def report_delay_penalty(graph):
                % (graph.delay_penalty, graph.entry_sum_total / max(n, 1), n))
 
 
+def spec_augment_keywords(args):
+    """--spec-augment: the graph keyword, empty without the flag.  The FATAL line and exit 1 for a value that
+    nnet.augment.parse_spec refuses, and for bins that do not divide the input_dim of a readable <nnet-config>.  Host work
+    only: runs BEFORE the device is set up."""
+    text = getattr(args, 'spec_augment', None)
+    if text is None:
+        return {}
+    from lstm_ctc_amd.nnet import augment
+    try:
+        spec = augment.parse_spec(text)
+    except ValueError as exc:                         # "spec-augment: ..." or "SpecAugment: ..."
+        _fatal('--%s' % exc if str(exc).startswith('spec-augment') else '--spec-augment: %s' % exc)
+    try:
+        from lstm_ctc_amd.nnet.config import parse_config
+        input_dim = parse_config(args.nnet_config).get('input_dim')
+    except (OSError, AttributeError):                 # an unreadable config is reported where it is read for the model
+        input_dim = None
+    if isinstance(input_dim, int):
+        try:
+            spec.check_layout(input_dim)
+        except ValueError as exc:
+            _fatal('--spec-augment: %s' % exc)
+    return {'spec_augment': spec}
+
+
+def report_spec_augment(graph):
+    """One INFO line at the end of a pass under --spec-augment: the settings, the steps augmented and how much of the input the
+    masks covered (nnet.augment.mask_plan on the sequence lengths the steps had on the host)."""
+    from lstm_ctc_amd.nnet import tflog
+    tflog.info('spec augment %s: %d step(s) augmented; %.2f%% of %d live raw frame(s) under a time mask, %.2f%% of the bins '
+               'under a frequency mask'
+               % (graph.spec_augment, graph.specaug_steps, 100.0 * graph.specaug_frames_masked / max(graph.specaug_frames, 1),
+                  graph.specaug_frames, 100.0 * graph.specaug_bins_masked / max(graph.specaug_bins, 1)))
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:
@@ -224,6 +259,11 @@ FLAGS = {
     '--delay-penalty': dict(type=float, default=None, help='with --objective ctc: weight every path by exp(-penalty * sum of the '
                             'frames at which its labels are entered), so that the model learns to emit earlier (new); needs no '
                             'table, composes with --align-window; 0 is plain CTC and reports the mean label entry frame'),
+    '--spec-augment': dict(type=str, default=None, help='SpecAugment on the device, training steps only (new): '
+                           'time=NxW,freq=NxW,bins=F[,cap=P][,fill=V] = N time masks of at most W raw frames (and at most P percent '
+                           'of the utterance, default 100), N frequency masks of at most W of the F bins of a feature group '
+                           '(statics, deltas, ...; F divides input_dim), masked elements set to V (default 0); e.g. '
+                           'time=2x40,freq=2x15,bins=40,cap=20'),
     '--optimizer': dict(type=str, default='sgd', help='sgd | momentum (0.9) | adam, constant learning rate'),
     '--evaluate': dict(type=str2bool, default='false', help='also report an error rate: greedy decoding and the token error rate (ctc), the frame error rate (xent)'),
     '--learn-rate': dict(type=float, default=0.0001, help='step size of the optimizer'),

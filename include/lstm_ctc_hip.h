@@ -521,6 +521,40 @@ int lc_length_mask(float *x, int T, int B, int C, int ldx, const int *seq_len, l
 int lc_pack_rows(const float *x, int ldx, const int *rows, int Mp, int C, float *out, int ldo, lc_stream_t stream);
 int lc_unpack_rows(const float *x, int ldx, const int *inverse, int rows, int C, float *out, int ldo, lc_stream_t stream);
 
+/* ------------------------------------------------------------------ SpecAugment ------------- */
+/* Time and frequency masking of the filterbank input (Park et al., 2019; no reference counterpart), on the spliced and
+ * subsampled batch the loader uploads.  x and out are time-major [T * B, D] with row pitches ldx / ldo (floats); out == x (in
+ * place) is allowed.
+ * Layout: with s = max(subsample, 1) and l, r the contexts, column c of row (t, b) belongs to spliced block i = c / base_dim;
+ * it shows raw frame u = clamp(t * s + i - l, 0, n - 1), n = seq_len[b] * s, and bin f = (c % base_dim) % freq_bins.
+ *   - the utterance is treated as having exactly n raw frames: the loader drops the T_raw % s tail, and the true raw length
+ *     does not reach the device;
+ *   - this is exact whenever r <= s - 1, which covers the recipes;
+ *   - otherwise the last rows' right-context copies of frames past n - 1 count as frame n - 1.
+ * Draws (all integer arithmetic): hash(k) = the 32-bit value lc_dropout_factor forms before its float conversion, for
+ * (seed, stream id 0x53504543, 64-bit index b * 32 + k); ranged(v, m) = ((uint64_t)v * m) >> 32.
+ *   time mask j < time_masks:  W = min(time_width, n * time_percent / 100) (64-bit integer division),
+ *                              w = ranged(hash(2j), W + 1), t0 = ranged(hash(2j + 1), n - w + 1): raw frames [t0, t0 + w)
+ *   freq mask j < freq_masks:  w = ranged(hash(16 + 2j), freq_width + 1), f0 = ranged(hash(17 + 2j), freq_bins - w + 1):
+ *                              bins [f0, f0 + w) of every feature group and every spliced block
+ * Masks are drawn per utterance, may overlap, and may have width 0.
+ * Output: for t < seq_len[b], out = fill where a time mask holds u or a frequency mask holds f, out = x bit for bit elsewhere;
+ * rows with t >= seq_len[b] are copied unchanged; every element of out is written on every call.  plan (device [B,16,2] int32,
+ * or NULL) receives (start, width) per mask: rows 0-7 the time masks, rows 8-15 the frequency masks, unused rows (0, 0).
+ * A pure function of its arguments (no atomics): the same call gives the same bits.
+ * LC_EINVAL, with nothing launched and no output touched: T, B, D <= 0; a NULL x / seq_len / cfg / out; a pitch below D; a mask
+ * count outside 0..8; a negative width; time_percent outside 0..100; freq_bins <= 0; base_dim % freq_bins != 0; freq_width >
+ * freq_bins; D != base_dim * (1 + l + r); negative contexts or subsample; a fill that is not finite.
+ * 16-byte accesses when D and both pitches are multiples of 4 and both bases 16-byte aligned, a scalar path otherwise. */
+typedef struct lc_spec_augment {
+    int time_masks, time_width, time_percent;   /* 0..8 masks; width cap in RAW frames; cap in percent of the utterance, 0..100 */
+    int freq_masks, freq_width, freq_bins;      /* 0..8 masks; width cap in bins; F = bins per feature group */
+    int base_dim, left_context, right_context, subsample;   /* the loader's layout: D = base_dim * (1 + l + r) */
+    float fill;                                 /* value written into masked elements (finite) */
+} lc_spec_augment_t;
+int lc_spec_augment(const float *x, int T, int B, int D, int ldx, const int *seq_len, const lc_spec_augment_t *cfg /* host */,
+                    uint32_t seed, float *out, int ldo, int *plan /* device [B,16,2] or NULL */, lc_stream_t stream);
+
 /* ------------------------------------------------------------------ development hook -------- */
 /* Not part of the product surface: when set to a device buffer of [T][4 waves][8] 64-bit words, one workgroup of
  * the forward step kernel stores s_memtime stamps of its phases there (tools/stamp_probe.py); NULL switches it off. */

@@ -76,6 +76,8 @@ SIGNATURES = {
     "lc_length_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lc_pack_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "lc_unpack_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "lc_spec_augment": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_u32, c_void_p, c_int, c_void_p,
+                                c_void_p]),
     "lc_lstm_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "lc_lstm_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
     "lc_lstm_fwd_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
@@ -119,6 +121,13 @@ class GemmEpilogue(ctypes.Structure):
     _fields_ = [("keep", ctypes.c_float), ("seed", ctypes.c_uint32), ("stream0", ctypes.c_uint32),
                 ("drop_width", ctypes.c_int), ("c_bf16", ctypes.c_void_p), ("ldc_bf16", ctypes.c_int),
                 ("shadow_only", ctypes.c_int)]
+
+
+class SpecAugmentConfig(ctypes.Structure):
+    """lc_spec_augment_t"""
+    _fields_ = [("time_masks", c_int), ("time_width", c_int), ("time_percent", c_int), ("freq_masks", c_int),
+                ("freq_width", c_int), ("freq_bins", c_int), ("base_dim", c_int), ("left_context", c_int),
+                ("right_context", c_int), ("subsample", c_int), ("fill", c_float)]
 
 
 class SeqExInfo(ctypes.Structure):

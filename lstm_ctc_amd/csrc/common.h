@@ -46,6 +46,13 @@ __host__ __device__ inline float lc_dropout_factor(uint32_t seed, uint32_t strea
     float u = (float)(v >> 8) * (1.0f / 16777216.0f);
     return u < keep ? inv_keep : 0.0f;
 }
+// The 32-bit value v that lc_dropout_factor forms before it converts to float: integer draws (lc_spec_augment) take it whole.
+__host__ __device__ inline uint32_t lc_hash_u32(uint32_t seed, uint32_t stream, uint64_t idx)
+{
+    uint32_t h = (seed * 0x9E3779B1u) ^ (stream * 0x85EBCA77u + 0x165667B1u);
+    uint32_t v = lc_fmix32((uint32_t)idx ^ h);
+    return lc_fmix32(v ^ ((uint32_t)(idx >> 32) + 0x27D4EB2Fu));
+}
 
 // ---- wave-level helpers (wave = 64 lanes on gfx950) ----
 // lane i receives x from lane i-1; lane 0 receives fill.   (DPP wave_shr:1)

@@ -5,6 +5,7 @@ liblstm_ctc_hip.so and is imported lazily so that CPU-only tooling can still rea
 """
 from .config import parse_config
 from .class_prior import get_class_prior
+from .augment import SpecAugment, parse_spec
 
 from .pipeline import create_pipeline_sequence_batch, create_pipeline_sequential
 from .tfrecord import dataset_from_tfrecords, write_tfrecord
@@ -15,7 +16,7 @@ __all__ = ["parse_config", "get_class_prior", "train", "validate", "create_graph
            "create_graph_for_validation_kd", "Session",
            "get_create_logits", "create_logits_blstm", "create_logits_lstm", "create_logits_cudnnlstm",
            "create_pipeline_sequence_batch", "create_pipeline_sequential", "dataset_from_tfrecords",
-           "write_tfrecord"]
+           "write_tfrecord", "SpecAugment", "parse_spec"]
 
 
 def __getattr__(name):

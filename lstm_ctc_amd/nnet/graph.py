@@ -161,11 +161,20 @@ class CTCGraph:
     penalised criterion; the output gains ``entry_sum`` (the expected sum of the label entry frames under the criterion's
     path posterior) and ``entry_labels`` (the labels of the utterances with a finite, non-skipped loss), so that
     ``entry_sum / entry_labels`` is the mean frame at which a label is entered; ``entry_sum_total`` / ``entry_labels_total``
-    sum over the steps.  0 is plain CTC plus the metric.  ``None`` is the step without it, untouched."""
+    sum over the steps.  0 is plain CTC plus the metric.  ``None`` is the step without it, untouched.
+
+    ``spec_augment=SpecAugment(...)`` (new, training graphs, every objective; ``nnet.augment``) masks the input of every
+    TRAINING step on the device: the model reads ``ops.spec_augment(x, ...)``, written OUT OF PLACE - the caller's ``x`` is
+    never changed, so ``step_device`` callers may pass the same tensor step after step.  The draws are seeded with the step's
+    ``drop_seed``: ranks and epochs differ, and a step re-run on the launch train repeats them.  The layout is
+    ``left_context`` / ``right_context`` / ``subsample`` / ``input_dim`` of ``nnet_config``.  ``train=False`` steps and
+    ``align`` never augment.  ``specaug_steps`` counts the augmented steps; ``specaug_frames_masked`` / ``specaug_frames`` and
+    ``specaug_bins_masked`` / ``specaug_bins`` sum the masked and the live raw frames and bins over the steps whose sequence
+    lengths were on the host (``step``; ``step_device`` with ``seq_host``).  ``None`` is the step without it, untouched."""
 
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None,
-                 teacher_weight=None, teacher_temperature=1.0, delay_penalty=None):
+                 teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
@@ -203,6 +212,16 @@ class CTCGraph:
             delay_penalty = float(delay_penalty)
         self.delay_penalty = delay_penalty
         self.entry_sum_total, self.entry_labels_total = 0.0, 0
+        self.spec_layout = None
+        if spec_augment is not None:
+            from . import augment
+            if not isinstance(spec_augment, augment.SpecAugment):
+                raise ValueError("spec_augment must be an nnet.augment.SpecAugment or None, got %r" % (spec_augment,))
+            self.spec_layout = augment.layout_of(nnet_config)
+            spec_augment.check_layout(self.spec_layout.base_dim)           # ValueError: freq_bins must divide input_dim
+        self.spec_augment = spec_augment
+        self.specaug_steps = 0
+        self.specaug_frames_masked = self.specaug_frames = self.specaug_bins_masked = self.specaug_bins = 0
         self.pipeline = pipeline
         self.model = Model(nnet_config, device, seed=seed)
         self.training = learn_rate is not None
@@ -443,7 +462,30 @@ class CTCGraph:
         ops.lstm_status(dev).zero_()
         self.global_step += 1
         self.drop_seed = (self.drop_seed * 1664525 + 1013904223) & 0x7FFFFFFF
+        specaug_counts = None
+        if train and self.spec_augment is not None:          # out of place: the caller keeps its x
+            x = ops.spec_augment(x, seq_d, self.spec_augment, self.spec_layout, self.drop_seed)
+            if seq_host is not None:
+                from . import augment
+                sub = self.spec_layout.subsample
+                specaug_counts = augment.masked_shares(augment.mask_plan(self.drop_seed, seq_host, self.spec_augment, sub),
+                                                       seq_host, self.spec_augment, sub)
         logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed, seq_len_host=seq_host)      # [T,B,V]
+        out, status = self._finish_step(logits, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host,
+                                        offs_host, frame_target, windows, teacher)
+        if status == 0 and train and self.spec_augment is not None:          # a failed step is re-run: count it once
+            self.specaug_steps += 1
+            if specaug_counts is not None:
+                self.specaug_frames_masked += specaug_counts[0]
+                self.specaug_frames += specaug_counts[1]
+                self.specaug_bins_masked += specaug_counts[2]
+                self.specaug_bins += specaug_counts[3]
+        return out, status
+
+    def _finish_step(self, logits, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
+                     frame_target, windows, teacher):
+        """What follows the forward in ``_step_once``: criterion, backward, optimizer, the step's one sync."""
+        dev = self.model.device
         if self.objective == "xent":
             return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train, teacher)
         if self.objective == "kd":
@@ -780,11 +822,11 @@ def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=N
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None,
-                                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None):
+                                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
                     align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature,
-                    delay_penalty=delay_penalty)
+                    delay_penalty=delay_penalty, spec_augment=spec_augment)
 
 
 def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None, teacher_weight=None,
@@ -796,10 +838,11 @@ def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=
 
 def create_graph_for_training_xent(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
                                    l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, teacher_weight=None,
-                                   teacher_temperature=1.0):
+                                   teacher_temperature=1.0, spec_augment=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
-                    objective="xent", teacher_weight=teacher_weight, teacher_temperature=teacher_temperature)
+                    objective="xent", teacher_weight=teacher_weight, teacher_temperature=teacher_temperature,
+                    spec_augment=spec_augment)
 
 
 def create_graph_for_validation_kd(pipeline, nnet_config, device="cuda", seed=None, teacher_temperature=1.0):
@@ -809,10 +852,11 @@ def create_graph_for_validation_kd(pipeline, nnet_config, device="cuda", seed=No
 
 
 def create_graph_for_training_kd(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
-                                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, teacher_temperature=1.0):
+                                 l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, teacher_temperature=1.0,
+                                 spec_augment=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
-                    objective="kd", teacher_temperature=teacher_temperature)
+                    objective="kd", teacher_temperature=teacher_temperature, spec_augment=spec_augment)
 
 
 def create_graph_for_alignment(pipeline, nnet_config, device="cuda"):

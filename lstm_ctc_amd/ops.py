@@ -744,6 +744,47 @@ def unpack_rows(x, inverse, out=None):
     return _gather_rows("lc_unpack_rows", x, inverse, out)
 
 
+# ------------------------------------------------------------------------------------------ SpecAugment
+def _tbd_pitch(t, T, B, D):
+    """Row pitch of a time-major [T, B, D] tensor whose T * B rows lie at one pitch (a column window of a wider buffer is
+    fine)."""
+    assert t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape) == (T, B, D), (t.dtype, tuple(t.shape))
+    assert D == 1 or t.stride(2) == 1, t.stride()
+    ld = t.stride(1) if B > 1 else (t.stride(0) if T > 1 else D)
+    assert ld >= D and (B == 1 or T == 1 or t.stride(0) == B * ld), t.stride()
+    return ld
+
+
+def spec_augment(x, seq_len, spec, layout, seed, out=None, plan=None):
+    """SpecAugment on the device (lc_spec_augment): x [T,B,D] time-major f32 (rows at one pitch), seq_len [B] i32, ``spec`` a
+    ``nnet.augment.SpecAugment``, ``layout`` = (base_dim, left_context, right_context, subsample) of the loader
+    (``nnet.augment.layout_of(nnet_config)``), ``seed`` the 32-bit seed of the draws.  Returns ``out`` (a new tensor unless
+    given; ``out=x`` masks in place): ``spec.fill`` where a time mask holds the element's raw frame or a frequency mask its
+    bin, x bit for bit elsewhere.  ``plan=True`` (or an int32 [B,16,2] tensor) also returns the (start, width) table of the
+    draws: ``(out, plan)``.  ``nnet.augment.apply_host`` / ``mask_plan`` are the same in numpy."""
+    lib = _lib.load()
+    _require_cuda(x, seq_len, out, plan if torch.is_tensor(plan) else None)
+    T, B, D = x.shape
+    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+    base_dim, left, right, subsample = (int(v or 0) for v in layout)
+    if out is None:
+        out = torch.empty((T, B, D), dtype=torch.float32, device=x.device)
+    if plan is True:
+        plan = torch.empty((B, 16, 2), dtype=torch.int32, device=x.device)
+    elif plan is False:
+        plan = None
+    if plan is not None:
+        assert plan.dtype == torch.int32 and tuple(plan.shape) == (B, 16, 2) and plan.is_contiguous()
+    cfg = _lib.SpecAugmentConfig(spec.time_masks, spec.time_width, spec.time_percent, spec.freq_masks, spec.freq_width,
+                                 spec.freq_bins, base_dim, left, right, subsample, spec.fill)
+    ev = _prof_begin()
+    _lib.check(lib.lc_spec_augment(_ptr(x), T, B, D, _tbd_pitch(x, T, B, D), _ptr(seq_len), ctypes.byref(cfg),
+                                   int(seed) & 0xFFFFFFFF, _ptr(out), _tbd_pitch(out, T, B, D), _ptr(plan), _stream()),
+               "lc_spec_augment")
+    _prof_end("specaug", 8.0 * T * B * D, ev)
+    return out if plan is None else (out, plan)
+
+
 # ------------------------------------------------------------------------------------------ bf16 shadow operands (c5)
 def cast_bf16(x, nat=True, tr=False, out_nat=None):
     """bf16 copies of the float32 matrix x [rows, C]: (nat [rows, C] or None, tr [C, rows8] or None), rows8 = rows
