@@ -222,6 +222,44 @@ def report_spec_augment(graph):
                   graph.specaug_frames, 100.0 * graph.specaug_bins_masked / max(graph.specaug_bins, 1)))
 
 
+def consistency_keywords(args, augmented):
+    """--consistency-weight: the graph keyword, empty without the flag.  ``augmented``: what spec_augment_keywords returned.
+    The FATAL line and exit 1 for a value that is not finite and > 0, another objective than ctc, --teacher-scores, and two
+    views that cannot differ (no --spec-augment while a readable <nnet-config> has no dropout).  Host work only: runs BEFORE
+    the device is set up."""
+    weight = getattr(args, 'consistency_weight', None)
+    if weight is None:
+        return {}
+    import math
+    if not (math.isfinite(weight) and weight > 0):
+        _fatal('--consistency-weight must be a finite number > 0, got %r' % weight)
+    if args.objective != 'ctc':
+        _fatal('--consistency-weight pairs two views under the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
+    if getattr(args, 'teacher_scores', None):
+        _fatal('--consistency-weight does not combine with --teacher-scores')
+    if not augmented:
+        try:
+            from lstm_ctc_amd.nnet.config import parse_config
+            from lstm_ctc_amd.nnet.graph import config_keep
+            keep = config_keep(dict(parse_config(args.nnet_config), is_training=True))
+        except (OSError, AttributeError):             # an unreadable config is reported where it is read for the model
+            keep = None
+        except (TypeError, ValueError) as exc:        # a dropout_rate that is no number
+            _fatal('--consistency-weight: cannot read dropout_rate of "%s": %s' % (args.nnet_config, exc))
+        if keep is not None and keep >= 1.0:
+            _fatal('--consistency-weight needs two views that differ: pass --spec-augment, or train a model with dropout '
+                   '("%s" has none)' % args.nnet_config)
+    return {'consistency_weight': weight}
+
+
+def report_consistency(graph):
+    """One INFO line at the end of a pass under --consistency-weight: how far apart the two views' posteriors were."""
+    from lstm_ctc_amd.nnet import tflog
+    n = graph.cr_frames_total
+    tflog.info('consistency weight %g: mean symmetric KL %.6f per frame over %d frame(s) of a pair, the argmaxes agree on %.2f%%'
+               % (graph.consistency_weight, graph.cr_loss_total / max(n, 1), n, 100.0 * graph.cr_agree_total / max(n, 1)))
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:
@@ -264,6 +302,10 @@ FLAGS = {
                            'of the utterance, default 100), N frequency masks of at most W of the F bins of a feature group '
                            '(statics, deltas, ...; F divides input_dim), masked elements set to V (default 0); e.g. '
                            'time=2x40,freq=2x15,bins=40,cap=20'),
+    '--consistency-weight': dict(type=float, default=None, help='with --objective ctc: consistency-regularised CTC (new): every '
+                                 'training step runs each utterance twice, under two draws of --spec-augment and dropout, and adds '
+                                 'weight * 0.5 * the symmetric KL between the two views\' frame posteriors to the CTC criterion of both '
+                                 '(a step then costs a batch of twice --batch-size); needs --spec-augment or a model with dropout'),
     '--optimizer': dict(type=str, default='sgd', help='sgd | momentum (0.9) | adam, constant learning rate'),
     '--evaluate': dict(type=str2bool, default='false', help='also report an error rate: greedy decoding and the token error rate (ctc), the frame error rate (xent)'),
     '--learn-rate': dict(type=float, default=0.0001, help='step size of the optimizer'),

@@ -6,13 +6,14 @@ import sys
 
 from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
                      report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, delay_keywords,
-                     report_delay_penalty, spec_augment_keywords, report_spec_augment)
+                     report_delay_penalty, spec_augment_keywords, report_spec_augment, consistency_keywords, report_consistency)
 
 
 def main(args):
     try:
         delayed = delay_keywords(args)                    # --delay-penalty; fatal before the device is touched
         augmented = spec_augment_keywords(args)           # --spec-augment; likewise
+        paired = consistency_keywords(args, augmented)    # --consistency-weight; likewise
         frame_targets = read_frame_targets(args)          # xent, or ctc with --align-window; fatal before the device is touched
         teacher = read_teacher_scores(args)               # --teacher-scores / --objective kd; likewise
         device, pg, rank, world = setup_device()
@@ -42,7 +43,7 @@ def main(args):
         windowed = {'align_window': args.align_window} if args.align_window is not None else {}
         graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, learn_rate=args.learn_rate,
                              clip_norm=args.clip_norm, optimizer=args.optimizer, device=device, seed=args.seed,
-                             process_group=pg, **windowed, **teacher_graph, **delayed, **augmented)
+                             process_group=pg, **windowed, **teacher_graph, **delayed, **augmented, **paired)
         graph.restore(args.nnet_in)                       # trainable variables only; Adam slots restart
         sess = nnet.Session(graph)
         nnet.train(sess=sess, graph=graph, evaluate=args.evaluate, report_interval=args.report_interval)
@@ -56,6 +57,8 @@ def main(args):
             report_delay_penalty(graph)
         if augmented:
             report_spec_augment(graph)
+        if paired:
+            report_consistency(graph)
         if rank == 0:
             tflog.info('saving nnet to "%s"' % args.nnet_out)
             graph.save(args.nnet_out)
@@ -69,7 +72,7 @@ if __name__ == '__main__':
     args = build_cli(('tfrecords_scp', 'nnet_config', 'nnet_in', 'nnet_out'),
                      ('--objective', '--optimizer', '--evaluate', '--learn-rate', '--batch-size', '--batch-threads',
                       '--seed', '--num-parallel-calls', '--report-interval', '--shuffle', '--clip-norm',
-                      '--frame-targets', '--align-window', '--delay-penalty', '--spec-augment', '--teacher-scores', '--teacher-domain', '--teacher-weight',
+                      '--frame-targets', '--align-window', '--delay-penalty', '--spec-augment', '--consistency-weight', '--teacher-scores', '--teacher-domain', '--teacher-weight',
                       '--teacher-temperature')).parse_args()
     sys.stderr.write('INFO:tensorflow:' + ' '.join(sys.argv) + '\n')
     main(args)

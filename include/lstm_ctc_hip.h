@@ -194,6 +194,38 @@ int lc_kd_loss(const float *logits, const float *teacher, int T, int B, int V, c
                float temperature, float grad_scale, float *loss, int *frames, int *agree, float *grad, int accumulate,
                void *workspace, size_t workspace_bytes, lc_stream_t stream);
 
+/* Consistency-regularised CTC (CR-CTC): the per-frame symmetric KL between the posteriors of two views of one utterance
+ * that sit in the two halves of ONE batch - lc_kd_loss's sibling, reading each row once.  No reference counterpart.
+ *   B       the number of PAIRS;
+ *   logits  [T,2B,V] time-major fp32: row (t, b) is view a of pair b, row (t, b + B) is view b;
+ *   seq_len [B] one length per pair.  A pair-frame (t, b) is SCORED when t < seq_len[b].
+ * With qa = softmax(za) and qb = softmax(zb) (natural log, no temperature):
+ *   loss [B]      sum over scored pair-frames of J = KL(qb || qa) + KL(qa || qb) = sum_k (qa_k - qb_k)(log qa_k - log qb_k);
+ *                 a class with probability 0 in both views contributes 0; NOT scaled by grad_scale and NOT clamped;
+ *   frames [B]    number of scored pair-frames;
+ *   agree [B]     scored pair-frames whose two argmaxes coincide (lowest index among equal maxima, lc_ctc_greedy's rule);
+ *   grad [T,2B,V] or NULL: on scored pair-frames row a gets grad_scale * (qa - qb) and row b grad_scale * (qb - qa).  This is
+ *                 the STOP-GRADIENT form - each view is a constant target for the other - and therefore NOT the derivative
+ *                 of J (it is that of KL(qb || qa) in za with qb held fixed, and of KL(qa || qb) in zb with qa held fixed).
+ *                 accumulate == 0: stored, every other row +0; accumulate != 0: added to what grad holds, every other row
+ *                 left bit-exactly as it was (neither read nor written).
+ * A row of EITHER view whose maximum is not finite (all -inf, a +inf) or that holds a NaN makes loss[b] NaN; its pair-frame
+ * counts nowhere and adds nothing to grad (two zero rows when storing).  A finite row with -inf entries behaves as float
+ * arithmetic gives: qa_k > 0 against zb_k = -inf is +inf loss and finite gradient rows.  An unscored pair-frame's rows are
+ * never read.  Every element of loss, frames and agree (and of grad when storing) is written on every call; results are
+ * bit-identical from call to call and with and without a gradient (no atomics: 8 bytes per pair-frame go to the workspace
+ * and a second launch folds each pair's terms in a fixed order in double, rounding once).  Arithmetic per pair-frame, fp32:
+ * a = za - max za, b = zb - max zb, d_k = exp(a_k) / Sa - exp(b_k) / Sb with Sa, Sb the two sums of exponentials, J =
+ * sum_{d_k != 0} d_k ((a_k - b_k) - (ln Sa - ln Sb)) - no per-element log, and exactly 0 (with a zero gradient) for two equal
+ * rows.  Rows of V <= 1024 are read once and kept in registers up to the gradient stores (V <= 64: four pair-frames per
+ * wave); wider rows are re-read.  T, B <= 0, V < 2, a grad_scale that is not finite, a NULL required pointer, or accumulate
+ * != 0 with grad == NULL: LC_EINVAL with no launch; a workspace below lc_consistency_workspace_bytes: LC_EWORKSPACE; both
+ * leave every output alone.  Elements are indexed in 64 bits (T * 2B * V may exceed 2^31). */
+size_t lc_consistency_workspace_bytes(int T, int B, int V);
+int lc_consistency_loss(const float *logits, int T, int B, int V, const int *seq_len, float grad_scale, float *loss,
+                        int *frames, int *agree, float *grad, int accumulate, void *workspace, size_t workspace_bytes,
+                        lc_stream_t stream);
+
 /* tf.edit_distance(hyp, truth, normalize=False) — nnet/graph.py:143-149.  HOST function on HOST
  * buffers (integer DP on a few hundred tokens; SURVEY.md §2a keeps it on the host). */
 int lc_edit_distance_host(const int *hyp, int hyp_stride, const int *hyp_len, const int *truth,

@@ -37,6 +37,9 @@ SIGNATURES = {
     "lc_kd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "lc_kd_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "lc_consistency_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "lc_consistency_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_size_t, c_void_p]),
     "lc_debug_ctc_align_phases": (None, [c_int]),
     "lc_edit_distance_host": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "lc_gemm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

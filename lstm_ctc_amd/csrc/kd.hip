@@ -32,13 +32,11 @@
 //      scored, 2 = argmaxes agree, 4 = bad teacher row) as ONE 8-byte word to the workspace, laid out [B,T].
 //   2. kd_fold_kernel: one workgroup per utterance folds its frames' terms in a FIXED order in double and rounds once.
 #include "common.h"
+#include "row_group.h"
 #include <math.h>
 
 #define KD_LOG2E 1.4426950408889634f
 #define KD_LN2 0.6931471805599453f
-#define KD_SCORED 1
-#define KD_AGREE 2
-#define KD_BAD 4
 #define KD_MAX_GRID 2048                 // blocks of four waves, as stream_grid in misc.hip
 // The wide kernel re-reads both rows of a frame twice, and finds them in the Infinity Cache only while the rows of ALL waves
 // in flight fit there: 2 rows x 4 V bytes x 4 waves per block.  Its grid is capped so that they take 128 MiB of the 256 (at
@@ -48,50 +46,6 @@
 #define KD_WIDE_MIN_GRID 256
 
 namespace {
-
-// ---- reductions over a group of G lanes (G = 16: one DPP row; G = 64: the wave); every lane of the group gets the result
-#define KD_ROW_BUTTERFLY(OP, v, T, TOI, FROMI)                                                                          \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0xB1, 0xf, 0xf, false)));  /* quad_perm [1,0,3,2] */   \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0x4E, 0xf, 0xf, false)));  /* quad_perm [2,3,0,1] */   \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0x141, 0xf, 0xf, false))); /* row_half_mirror */       \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0x140, 0xf, 0xf, false)))  /* row_mirror */
-__device__ __forceinline__ int kd_mini(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int kd_id(int a) { return a; }
-
-template <int G> __device__ __forceinline__ float kd_max(float v)
-{
-    if (G == 64) return lc_wave_max(v);
-    KD_ROW_BUTTERFLY(fmaxf, v, float, __float_as_int, __int_as_float);
-    return v;
-}
-template <int G> __device__ __forceinline__ float kd_sum(float v)
-{
-    if (G == 64) return lc_wave_sum(v);
-    KD_ROW_BUTTERFLY(lc_addf, v, float, __float_as_int, __int_as_float);
-    return v;
-}
-template <int G> __device__ __forceinline__ int kd_min(int v)
-{
-    KD_ROW_BUTTERFLY(kd_mini, v, int, kd_id, kd_id);
-    if (G == 64) {
-        const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-        const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-        v = kd_mini(kd_mini(a, b), kd_mini(c, d));
-    }
-    return v;
-}
-
-// The waves walk the frames f = t * B + b with a grid stride; (t, b) are carried along by additions.
-struct KdWalk {
-    int t0, b0, st, sb;
-    __device__ __forceinline__ KdWalk(int first, int stride, int B) : t0(first / B), b0(first % B), st(stride / B), sb(stride % B) {}
-    __device__ __forceinline__ void next(int B)
-    {
-        t0 += st;
-        b0 += sb;
-        if (b0 >= B) { b0 -= B; ++t0; }
-    }
-};
 
 // one element of a frame: a = s - ms, b = z - mz on entry; the exponentials on exit; the KL sum gains ep (a - b) where ep > 0
 __device__ __forceinline__ void kd_element(float &s, float &z, float ms, float mz, float c, float &sp, float &sq, float &ka)
@@ -123,7 +77,7 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(const float *__restrict__ 
     const int stride = (int)gridDim.x * 4 * FW;      // <= 2048 * 16 frames per pass
     const int first = ((int)blockIdx.x * 4 + ((int)threadIdx.x >> 6)) * FW;
     const long long TB = (long long)T * B;
-    KdWalk w(first, stride, B);
+    RgWalk w(first, stride, B);
     for (long long fb = first; fb < TB; fb += stride, w.next(B)) {
         int b = w.b0 + g, t = w.t0;
 #pragma unroll
@@ -189,8 +143,8 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(const float *__restrict__ 
             ms = fmaxf(ms, s[j]);
             mz = fmaxf(mz, z[j]);
         }
-        ms = kd_max<G>(ms);
-        mz = kd_max<G>(mz);
+        ms = rg_max<G>(ms);
+        mz = rg_max<G>(mz);
         // lowest index holding each maximum (idx rises with j inside a lane)
         int cs = 0x7fffffff, cz = 0x7fffffff;
 #pragma unroll
@@ -199,18 +153,18 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(const float *__restrict__ 
             cs = s[j] == ms ? e : cs;
             cz = z[j] == mz ? e : cz;
         }
-        const bool same = kd_min<G>(cs) == kd_min<G>(cz);
+        const bool same = rg_min<G>(cs) == rg_min<G>(cz);
         float sp = 0.0f, sq = 0.0f, ka = 0.0f;
 #pragma unroll
         for (int j = 0; j < NE; ++j) kd_element(s[j], z[j], ms, mz, c, sp, sq, ka);
-        sp = kd_sum<G>(sp);
-        sq = kd_sum<G>(sq);
-        ka = kd_sum<G>(ka);
+        sp = rg_sum<G>(sp);
+        sq = rg_sum<G>(sq);
+        ka = rg_sum<G>(ka);
         const bool bad = scored && !(sp == sp);      // NaN exactly when the teacher row's maximum is not finite or it holds a NaN
         const bool good = scored && !bad;
         if (valid && l == 0)
             terms[bt] = make_int2(good ? __float_as_int(kd_term(ka, sp, sq, itau)) : 0,
-                                  good ? (KD_SCORED | (same ? KD_AGREE : 0)) : (bad ? KD_BAD : 0));
+                                  good ? (RG_SCORED | (same ? RG_AGREE : 0)) : (bad ? RG_BAD : 0));
         if (grad && valid && (good || !acc)) {
             const float ip = good ? scale * __builtin_amdgcn_rcpf(sp) : 0.0f, iq = good ? scale * __builtin_amdgcn_rcpf(sq) : 0.0f;
             if (VEC) {
@@ -277,7 +231,7 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
     const int stride = (int)gridDim.x * 4;
     const int first = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
     const long long TB = (long long)T * B;
-    KdWalk w(first, stride, B);
+    RgWalk w(first, stride, B);
     for (long long fb = first; fb < TB; fb += stride, w.next(B)) {
         const int b = w.b0, t = w.t0;
         const size_t bt = (size_t)b * T + t;
@@ -308,7 +262,7 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
         const float lms = ms, lmz = mz;
         ms = lc_wave_max(ms);
         mz = lc_wave_max(mz);
-        const bool same = kd_min<64>(lms == ms ? cs : 0x7fffffff) == kd_min<64>(lmz == mz ? cz : 0x7fffffff);
+        const bool same = rg_min<64>(lms == ms ? cs : 0x7fffffff) == rg_min<64>(lmz == mz ? cz : 0x7fffffff);
         // pass 2: the three sums, per lane in the order of its visits, then over the lanes
         float sp = 0.0f, sq = 0.0f, ka = 0.0f;
         kd_walk_row<VEC>(lane, V, head,
@@ -329,7 +283,7 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
         const bool good = sp == sp;                  // a NaN teacher slips past the maximum (comparisons), not past the sum
         if (lane == 0)
             terms[bt] = make_int2(good ? __float_as_int(kd_term(ka, sp, sq, itau)) : 0,
-                                  good ? (KD_SCORED | (same ? KD_AGREE : 0)) : KD_BAD);
+                                  good ? (RG_SCORED | (same ? RG_AGREE : 0)) : RG_BAD);
         // pass 3: the gradient row
         if (gr && (good || !acc)) {
             const float ip = good ? scale * __builtin_amdgcn_rcpf(sp) : 0.0f, iq = good ? scale * __builtin_amdgcn_rcpf(sq) : 0.0f;
@@ -358,54 +312,18 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------ 2. per-utterance fold
-__device__ __forceinline__ double kd_xor_d(double x, int mask)
-{
-    const int lo = __shfl_xor(__double2loint(x), mask, 64), hi = __shfl_xor(__double2hiint(x), mask, 64);
-    return __hiloint2double(hi, lo);
-}
 __global__ __launch_bounds__(256) void kd_fold_kernel(const int2 *__restrict__ terms, int T, float *__restrict__ loss,
                                                       int *__restrict__ frames, int *__restrict__ agree)
 {
-    __shared__ double sacc[4];
-    __shared__ int sn[4], sc[4], sbad[4];
-    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
-    const int2 *row = terms + (size_t)b * T;
-    double acc = 0.0;
-    int n = 0, c = 0, bad = 0;
-    for (int t = tid; t < T; t += 256) {             // thread i: frames i, i + 256, ... in sequence
-        const int2 w = row[t];
-        if (w.y & KD_SCORED) {
-            acc += (double)__int_as_float(w.x);
-            ++n;
-            c += (w.y & KD_AGREE) ? 1 : 0;
-        }
-        bad |= w.y & KD_BAD;
-    }
-#pragma unroll
-    for (int mask = 1; mask < 64; mask <<= 1) {      // both lanes of a pair add the same two operands: one result, fixed order
-        acc += kd_xor_d(acc, mask);
-        n += __shfl_xor(n, mask, 64);
-        c += __shfl_xor(c, mask, 64);
-        bad |= __shfl_xor(bad, mask, 64);
-    }
-    if ((tid & 63) == 0) { sacc[wave] = acc; sn[wave] = n; sc[wave] = c; sbad[wave] = bad; }
-    __syncthreads();
-    if (tid == 0) {
-        const double total = (sacc[0] + sacc[1]) + (sacc[2] + sacc[3]);
-        loss[b] = (sbad[0] | sbad[1] | sbad[2] | sbad[3]) ? __int_as_float(0x7fc00000) : (float)total;
-        frames[b] = sn[0] + sn[1] + sn[2] + sn[3];
-        agree[b] = sc[0] + sc[1] + sc[2] + sc[3];
-    }
+    rg_fold(terms, T, loss, frames, agree);
 }
-
-inline size_t kd_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
 extern "C" size_t lc_kd_workspace_bytes(int T, int B, int V)
 {
     if (T <= 0 || B <= 0 || V < 2) return 0;
-    return kd_align256((size_t)T * B * sizeof(int2));              // per frame: its term (float) and a flag word
+    return rg_align256((size_t)T * B * sizeof(int2));              // per frame: its term (float) and a flag word
 }
 
 extern "C" int lc_kd_loss(const float *logits, const float *teacher, int T, int B, int V, const int *seq_len,

@@ -22,13 +22,18 @@ class _Running:
         self.processed = 0
         self.loss = 0.0
         self.acc = 0.0 if evaluate else None
+        self.evaluated = 0
 
-    def update(self, size, eval_loss, batch_eval):
+    def update(self, size, eval_loss, batch_eval, eval_size=None):
+        """``eval_size``: what ``batch_eval`` was counted against when that is not ``size`` (a graph with consistency_weight
+        reports the loss over both views' labels and the edit distance of view a alone); None: ``size``."""
         if size > 0:
             self.processed += size
             self.loss += (eval_loss / size - self.loss) * size / self.processed
-            if self.acc is not None:
-                self.acc += (batch_eval / size - self.acc) * size / self.processed
+        eval_size = size if eval_size is None else eval_size
+        if self.acc is not None and eval_size > 0:
+            self.evaluated += eval_size
+            self.acc += (batch_eval / eval_size - self.acc) * eval_size / self.evaluated
         self.step += 1
 
 
@@ -139,7 +144,10 @@ def _loop(sess, graph, evaluate, report_interval, nodes, tag):
             thr.update(values.get("sequence_length"))
             size, eval_loss, batch_eval = _reduce_triple(graph, values["size"], values["eval_loss"],
                                                          values.get("eval") if evaluate else None)
-            run.update(size, eval_loss, batch_eval)
+            eval_size = values.get("eval_size") if evaluate else None
+            if eval_size is not None:                     # summed over ranks like the triple; only such graphs pay for it
+                eval_size = _reduce_triple(graph, eval_size, 0.0, None)[0]
+            run.update(size, eval_loss, batch_eval, eval_size)
             if report_interval and run.step % report_interval == 0:
                 log = "step = %d, batch_size = %d, loss = %f" % (run.step, size, run.loss)
                 if evaluate:
@@ -168,6 +176,8 @@ def train(sess, graph, evaluate=False, report_interval=None):
              "eval_loss": graph["eval_loss"], "sequence_length": graph["sequence_length"]}
     if evaluate:
         nodes["eval"] = graph["eval"]
+        if "eval_size" in getattr(graph, "keys", ()):     # only a graph with consistency_weight has the node
+            nodes["eval_size"] = graph["eval_size"]
     _loop(sess, graph, evaluate, report_interval, nodes, "tr_loss")
     return True
 

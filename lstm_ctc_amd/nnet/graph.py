@@ -17,7 +17,7 @@ import torch
 
 from .. import ops
 from . import dp
-from .model import Model
+from .model import Model, config_keep
 
 
 class OutOfRangeError(Exception):
@@ -34,6 +34,16 @@ def flatten_labels(dense):
     offs = np.zeros(len(lens) + 1, np.int32)
     np.cumsum(lens, out=offs[1:])
     return flat, offs, int(lens.max()) if len(lens) else 0
+
+
+def double_batch(seq, flat, offs, win_lo=None, win_hi=None):
+    """consistency_weight: the batch with every utterance twice, utterance b again in place b + B - numpy arrays or tensors
+    alike.  (seq [2B], flat, offsets [2B+1], win_lo, win_hi): lengths, labels and label windows repeated, the second copy's
+    offsets shifted by the first copy's label count ``offs[-1]``; an argument that is None stays None.  The first halves ARE
+    the original batch."""
+    cat = torch.cat if torch.is_tensor(offs) else np.concatenate
+    twice = lambda a: None if a is None else cat([a, a])
+    return twice(seq), twice(flat), cat([offs, offs[1:] + offs[-1]]), twice(win_lo), twice(win_hi)
 
 
 def _label_smoothing_setup(nnet_config, device):
@@ -170,11 +180,30 @@ class CTCGraph:
     ``left_context`` / ``right_context`` / ``subsample`` / ``input_dim`` of ``nnet_config``.  ``train=False`` steps and
     ``align`` never augment.  ``specaug_steps`` counts the augmented steps; ``specaug_frames_masked`` / ``specaug_frames`` and
     ``specaug_bins_masked`` / ``specaug_bins`` sum the masked and the live raw frames and bins over the steps whose sequence
-    lengths were on the host (``step``; ``step_device`` with ``seq_host``).  ``None`` is the step without it, untouched."""
+    lengths were on the host (``step``; ``step_device`` with ``seq_host``).  ``None`` is the step without it, untouched.
+
+    ``consistency_weight=alpha`` (new, ``objective="ctc"`` training graphs; a finite float > 0) is consistency-regularised
+    CTC (CR-CTC, Yao et al. 2024).  Every TRAINING step runs on the batch with each utterance twice (``double_batch``:
+    utterance b again in column b + B; spec-augment masks and dropout are hashes of the column, so the two copies are two
+    independent views), takes the criterion (plain, windowed or delay-penalised) and the label-smoothing term on all 2B
+    columns, and adds ``alpha * 0.5 * sum J``, J = KL(qb || qa) + KL(qa || qb) per frame of a pair, through
+    ``ops.consistency_loss(logits, seq, grad_scale=0.5 * alpha, grad=grad)`` in its STOP-GRADIENT form (each view a fixed
+    target for the other).  NORMALISATION: the project's loss is a SUM over utterances, so the step is exactly "a batch of 2B
+    utterances plus alpha * 0.5 * J" - the CTC part is not halved; pick batch size and learning rate accordingly.  ``size``
+    counts the labels of both views, ``eval_loss`` is the criterion summed over both, ``loss`` gains the term, ``eval`` (when
+    fetched) is the edit distance of view a alone against the original labels, and ``eval_size`` comes with it: the number
+    of those labels, half of ``size`` - the error RATE is ``eval / eval_size`` (the run loops divide by it), never ``eval /
+    size``; ``sequence_length`` holds the lengths of both views, so that frames per second count what the device processed;
+    the output gains ``cr_loss`` (the plain sum
+    of J), ``cr_frames`` and ``cr_agree`` (frames of a pair scored / with equal argmaxes), in the step's one copy;
+    ``cr_loss_total`` / ``cr_frames_total`` / ``cr_agree_total`` sum over the steps; the spec-augment shares count both
+    views.  It needs two views that differ - ``spec_augment`` or dropout - and does not combine with ``teacher_weight``.
+    ``train=False`` steps and ``align`` never double.  ``None`` is the step without it, untouched."""
 
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None,
-                 teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None):
+                 teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None,
+                 consistency_weight=None):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
@@ -221,6 +250,22 @@ class CTCGraph:
             spec_augment.check_layout(self.spec_layout.base_dim)           # ValueError: freq_bins must divide input_dim
         self.spec_augment = spec_augment
         self.specaug_steps = 0
+        if consistency_weight is not None:
+            if objective != "ctc":
+                raise ValueError("consistency_weight pairs two views under the CTC criterion: it needs objective=\"ctc\", "
+                                 "not \"%s\"" % objective)
+            if (isinstance(consistency_weight, bool)
+                    or not isinstance(consistency_weight, (int, float, np.integer, np.floating))
+                    or not np.isfinite(consistency_weight) or not consistency_weight > 0):
+                raise ValueError("consistency_weight must be a finite float > 0 or None, got %r" % (consistency_weight,))
+            if teacher_weight is not None:
+                raise ValueError("consistency_weight does not combine with teacher_weight (a doubled teacher tensor is not built)")
+            if spec_augment is None and config_keep(nnet_config) >= 1.0:
+                raise ValueError("consistency_weight needs two views that differ: spec_augment or dropout (the model has "
+                                 "neither, the term would be 0)")
+            consistency_weight = float(consistency_weight)
+        self.consistency_weight = consistency_weight
+        self.cr_loss_total, self.cr_frames_total, self.cr_agree_total = 0.0, 0, 0
         self.specaug_frames_masked = self.specaug_frames = self.specaug_bins_masked = self.specaug_bins = 0
         self.pipeline = pipeline
         self.model = Model(nnet_config, device, seed=seed)
@@ -260,6 +305,8 @@ class CTCGraph:
             self.sm_weight, self.sm_logq = _label_smoothing_setup(nnet_config, dev)
         self.keys = ["nnet_input", "sequence_length", "logits", "raw_target", "nnet_target", "size", "eval_loss",
                      "loss", "eval", "global_step", "summary"] + (["lrate", "train"] if self.training else [])
+        if self.consistency_weight is not None:
+            self.keys.append("eval_size")                # what ``eval`` is to be divided by: ``size`` counts both views
 
     # the reference's graph is a dict; give the same key access
     def __contains__(self, key):
@@ -412,7 +459,7 @@ class CTCGraph:
         out = self.step_device(x, seq_d, flat_d, offs_d, maxlen, int(len(flat)), fetch_eval=fetch_eval,
                                fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs, seq_host=seq,
                                frame_target=ft_d, windows=windows, teacher=teacher)
-        out["sequence_length"] = seq
+        out["sequence_length"] = np.concatenate([seq, seq]) if "cr_loss" in out else seq      # what the device processed
         return out
 
     def step_device(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval=False, fetch_logits=False, train=None,
@@ -462,6 +509,18 @@ class CTCGraph:
         ops.lstm_status(dev).zero_()
         self.global_step += 1
         self.drop_seed = (self.drop_seed * 1664525 + 1013904223) & 0x7FFFFFFF
+        pairs = None
+        if train and self.consistency_weight is not None:    # every utterance twice; out of place: the caller keeps its x
+            pairs = seq_d
+            x = torch.cat([x, x], dim=1)
+            lo_d, hi_d = windows if windows is not None else (None, None)
+            seq_d, flat_d, offs_d, lo_d, hi_d = double_batch(seq_d, flat_d, offs_d, lo_d, hi_d)
+            windows = (lo_d, hi_d) if windows is not None else None
+            if seq_host is not None:
+                seq_host = np.concatenate([seq_host, seq_host])
+            if offs_host is not None:
+                _, flat_host, offs_host, _, _ = double_batch(None, flat_host, np.asarray(offs_host))
+            size = 2 * size
         specaug_counts = None
         if train and self.spec_augment is not None:          # out of place: the caller keeps its x
             x = ops.spec_augment(x, seq_d, self.spec_augment, self.spec_layout, self.drop_seed)
@@ -472,7 +531,7 @@ class CTCGraph:
                                                        seq_host, self.spec_augment, sub)
         logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed, seq_len_host=seq_host)      # [T,B,V]
         out, status = self._finish_step(logits, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host,
-                                        offs_host, frame_target, windows, teacher)
+                                        offs_host, frame_target, windows, teacher, pairs)
         if status == 0 and train and self.spec_augment is not None:          # a failed step is re-run: count it once
             self.specaug_steps += 1
             if specaug_counts is not None:
@@ -483,8 +542,9 @@ class CTCGraph:
         return out, status
 
     def _finish_step(self, logits, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
-                     frame_target, windows, teacher):
-        """What follows the forward in ``_step_once``: criterion, backward, optimizer, the step's one sync."""
+                     frame_target, windows, teacher, pairs=None):
+        """What follows the forward in ``_step_once``: criterion, backward, optimizer, the step's one sync.  ``pairs``: the [B]
+        lengths of a batch that ``_step_once`` doubled for consistency_weight (everything else is then the 2B batch)."""
         dev = self.model.device
         if self.objective == "xent":
             return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train, teacher)
@@ -508,6 +568,8 @@ class CTCGraph:
             reg = ops.label_smoothing(logits.view(T_ * B_, V_), self.sm_weight, self.sm_logq,
                                       grad.view(T_ * B_, V_) if train else None)
         kd = self._teacher_term(logits, seq_d, teacher, grad, train)
+        if pairs is not None:                              # teacher_weight is excluded: the two share kd's place in the word
+            kd = ops.consistency_loss(logits, pairs, grad_scale=0.5 * self.consistency_weight, grad=grad)[:3]
         if fetch_eval:
             tokens, out_len = ops.ctc_greedy(logits, seq_d)
         bn_saved = None
@@ -532,7 +594,13 @@ class CTCGraph:
             self.model.update_moving_averages(bn_saved)   # batch-norm UPDATE_OPS (graph.py:194-196); only with use_bn
         out["eval_loss"] = eval_loss
         out["loss"] = eval_loss + (float(reg.item()) if reg is not None else 0.0)
-        if kd is not None:
+        if pairs is not None:
+            out["cr_loss"], out["cr_frames"], out["cr_agree"] = float(word[1]), int(word[2]), int(word[3])
+            self.cr_loss_total += out["cr_loss"]
+            self.cr_frames_total += out["cr_frames"]
+            self.cr_agree_total += out["cr_agree"]
+            out["loss"] += self.consistency_weight * 0.5 * out["cr_loss"]
+        elif kd is not None:
             out["loss"] += self._kd_outputs(out, word[1:4])
         if entry_b is not None:
             out["entry_sum"], out["entry_labels"] = float(word[-2]), int(word[-1])
@@ -542,6 +610,11 @@ class CTCGraph:
             tok, n = tokens.cpu().numpy(), out_len.cpu().numpy()
             if flat_host is None:
                 flat_host, offs_host = flat_d.cpu().numpy(), offs_d.cpu().numpy()
+            if pairs is not None:                          # view a against the original labels: the first halves
+                B_ = pairs.numel()
+                tok, n, offs_host = tok[:B_], n[:B_], offs_host[:B_ + 1]
+                flat_host = flat_host[:offs_host[-1]]
+                out["eval_size"] = size // 2               # the labels ``eval`` was counted against
             out["eval"] = float(ops.edit_distance_host(tok, n, flat_host, offs_host).sum())   # graph.py:143-150
             out["decoded"] = (tok, n)
         if fetch_logits:
@@ -822,11 +895,12 @@ def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=N
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None,
-                                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None):
+                                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None,
+                                  consistency_weight=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
                     align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature,
-                    delay_penalty=delay_penalty, spec_augment=spec_augment)
+                    delay_penalty=delay_penalty, spec_augment=spec_augment, consistency_weight=consistency_weight)
 
 
 def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None, teacher_weight=None,

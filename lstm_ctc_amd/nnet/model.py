@@ -251,6 +251,16 @@ def _x3_pays(M, N, K, split_k=False):
     return tiles >= 128 and tiles * 100 >= rounds * 256 * X3_MIN_FILL
 
 
+def config_keep(cfg):
+    """The dropout keep probability a Model built from ``cfg`` runs with (1.0 = no dropout), without building it:
+    ``dropout_rate`` while training (bilstm.py:98-101), 1.0 otherwise and for cudnnlstm (lstm.py:26-122: no DropoutWrapper)."""
+    is_training = cfg.get("is_training")
+    dr = cfg.get("dropout_rate")
+    if dr is None or not (True if is_training is None else bool(is_training)) or cfg.get("nnet_type") == "cudnnlstm":
+        return 1.0
+    return float(dr)
+
+
 class Model:
     """Forward / backward of the stack on one batch.  ``x`` is time-major ``[T,B,D]`` on the GPU,
     zero beyond each utterance's length (the pipeline's padding value, nnet/pipeline.py:44)."""
@@ -262,10 +272,7 @@ class Model:
         self.ps.init_random(seed)
         is_training = self.cfg.get("is_training")
         self.is_training = True if is_training is None else bool(is_training)
-        dr = self.cfg.get("dropout_rate")
-        self.keep = float(dr) if (dr is not None and self.is_training) else 1.0      # bilstm.py:98-101
-        if self.ps.cudnn:
-            self.keep = 1.0                                                          # lstm.py:26-122: no DropoutWrapper
+        self.keep = config_keep(self.cfg)
         mt = self.cfg.get("moe_temp")
         self.tau = 10.0 if mt is None else float(mt)                                 # bilstm.py:74-76
         self.forget_bias = 5.0 if self.ps.blstm else 1.0                             # bilstm.py:133 / TF default

@@ -472,6 +472,44 @@ def kd_loss(logits, teacher, seq_len, teacher_len, temperature=1.0, grad_scale=1
     return loss, frames, agree, grad
 
 
+def consistency_loss(logits, seq_len, grad_scale=1.0, grad=None, want_grad=True):
+    """Consistency-regularised CTC's pair term - no reference counterpart.  logits [T,2B,V] f32: column b is view a of pair b,
+    column b + B its view b; seq_len [B] int32, one length per PAIR.  A pair-frame is scored when t < seq_len[b].  Returns
+    (loss [B] f32, frames [B] int32, agree [B] int32, grad) on the device: the summed J = KL(qb || qa) + KL(qa || qb) of the
+    scored pair-frames (not scaled), their number, how many of them have the two argmaxes coincide, and the STOP-GRADIENT
+    rows grad_scale * (qa - qb) / grad_scale * (qb - qa) (each view a constant target for the other: not the derivative of
+    J).  ``grad=None`` allocates a [T,2B,V] tensor and overwrites it (zero rows on pair-frames that are not scored); a given
+    tensor is accumulated into (rows that are not scored stay untouched); ``want_grad=False`` with ``grad=None`` computes no
+    gradient and returns None."""
+    lib = _lib.load()
+    _require_cuda(logits, seq_len, grad)
+    logits = _f32c(logits)
+    T, B2, V = logits.shape
+    assert seq_len.dtype == torch.int32
+    B = seq_len.numel()
+    if B2 != 2 * B or B == 0:
+        raise ValueError("consistency_loss: logits must be [T, 2B, V] for seq_len [B] (got %s, %s)"
+                         % (tuple(logits.shape), tuple(seq_len.shape)))
+    accumulate = grad is not None
+    if accumulate:
+        if grad.dtype != torch.float32 or tuple(grad.shape) != (T, B2, V) or not grad.is_contiguous():
+            raise ValueError("consistency_loss: grad must be a contiguous float32 [T, 2B, V] tensor to accumulate into")
+    elif want_grad:
+        grad = torch.empty_like(logits)
+    dev = logits.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    agree = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.lc_consistency_workspace_bytes(T, B, V)
+    ws = workspace("consistency", nbytes, dev)
+    ev = _prof_begin()
+    _lib.check(lib.lc_consistency_loss(_ptr(logits), T, B, V, _ptr(seq_len.contiguous()), float(grad_scale), _ptr(loss),
+                                       _ptr(frames), _ptr(agree), _ptr(grad), 1 if accumulate else 0, _ptr(ws), nbytes,
+                                       _stream()), "lc_consistency_loss")
+    _prof_end("consistency", (T, B, V), ev)
+    return loss, frames, agree, grad
+
+
 def alignment_segments(ali, label_index, seq_len):
     """HOST function on numpy arrays: ali / label_index [B,T] and seq_len [B] as :func:`ctc_align` returns them ->
     per utterance a list of (label, start_frame, num_frames) runs of non-blank frames.  A run ends where label_index
