@@ -29,6 +29,7 @@ long lc_option(int opt, long dflt);
     } while (0)
 
 static inline int lc_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline size_t lc_align256(size_t x) { return (x + 255) & ~(size_t)255; }      // workspace slabs start on 256 bytes
 
 // Counter-based dropout mask shared bit-for-bit with oracle/oracle.py:dropout_mask.
 // Returns 1/keep with probability keep, else 0.

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void cr_fold_kernel(const int2 *__restrict__ t
 extern "C" size_t lc_consistency_workspace_bytes(int T, int B, int V)
 {
     if (T <= 0 || B <= 0 || V < 2) return 0;
-    return rg_align256((size_t)T * B * sizeof(int2));              // per pair-frame: its term (float) and a flag word
+    return lc_align256((size_t)T * B * sizeof(int2));              // per pair-frame: its term (float) and a flag word
 }
 
 extern "C" int lc_consistency_loss(const float *logits, int T, int B, int V, const int *seq_len, float grad_scale, float *loss,

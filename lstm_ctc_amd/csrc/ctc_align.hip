@@ -2,7 +2,7 @@
 // No reference counterpart (TF 1.8 has no such op).  DESIGN.md section 3.6.
 //
 // Three launches per call, one wave per work item, no LDS, no atomics (the result is bit-identical from call to call):
-//   1. align_lse_kernel        one wave per live frame (t, b): lse[t, b] = log sum_k exp(logits[t, b, k]), fp32.
+//   1. lat_lse_kernel          (ctc_lattice.h) one wave per live frame (t, b): lse[t, b] = log sum_k exp(logits[t, b, k]), fp32.
 //   2. align_sweep_kernel<PPL> one wave per utterance.  Lane l holds the PPL consecutive lattice positions l * PPL .. l * PPL +
 //      PPL - 1 in registers, so the s-1 / s-2 neighbours are in the lane itself except for position l * PPL (and, with one
 //      position per lane, its s-2): those come by one DPP wave shift.  The cell values are DOUBLES: a cell's emission is the
@@ -19,47 +19,10 @@
 // Tie rule (fp32 inputs, exact comparisons): at a cell stay wins over s-1 wins over s-2 (a candidate replaces the incumbent only
 // when strictly greater); at the end S-1 wins over S-2.
 #include "common.h"
+#include "ctc_lattice.h"
 #include <math.h>
 
-#define AL_LOG2E 1.4426950408889634f
-#define AL_LN2 0.6931471805599453f
-
 static int g_align_phases = 7;      // development hook: bit 0 = lse pass, bit 1 = sweep, bit 2 = backtrace
-
-// ------------------------------------------------------------------------------------------ 1. per-frame log-sum-exp
-__global__ __launch_bounds__(256) void align_lse_kernel(const float *__restrict__ logits, int T, int B, int V,
-                                                        const int *__restrict__ seq_len, float *__restrict__ lse)
-{
-    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= (size_t)T * B) return;
-    const int t = (int)(row / B), b = (int)(row % B);
-    if (t >= seq_len[b]) return;                                  // never read by the sweep
-    const float *x = logits + row * V;
-    float m = -INFINITY;
-    for (int k = lane; k < V; k += 64) m = fmaxf(m, x[k]);
-    m = lc_wave_max(m);
-    float s = 0.0f;
-    for (int k = lane; k < V; k += 64) s += __builtin_amdgcn_exp2f((x[k] - m) * AL_LOG2E);
-    s = lc_wave_sum(s);
-    if (lane == 0) lse[row] = m + __builtin_amdgcn_logf(s) * AL_LN2;
-}
-
-// ------------------------------------------------------------------------------------------ helpers
-__device__ __forceinline__ double al_neg_inf() { return __longlong_as_double(0xfff0000000000000ull); }
-// lane i receives x of lane i-1, lane 0 receives -inf (two 32-bit DPP wave_shr:1 moves)
-__device__ __forceinline__ double al_shr1(double x)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)0xfff00000, __double2hiint(x), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double al_readlane(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
 
 // geometry shared by the sweep and the backtrace: words per lane and frame, frames per word
 template <int PPL> struct AlGeo {
@@ -85,7 +48,7 @@ __global__ __launch_bounds__(64) void align_sweep_kernel(const float *__restrict
     const int Tb = min(max(seq_len[b], 0), T);
     const int off = offs[b], L = offs[b + 1] - off, S = 2 * L + 1;
     const int blank = V - 1;
-    const double NEG = al_neg_inf();
+    const double NEG = lat_neg_inf();
     if (Tb == 0 || L < 0 || S > 64 * PPL) {
         if (lane == 0) { score[b] = Tb == 0 ? 0.0f : -INFINITY; endstate[b] = -1; }
         return;
@@ -137,8 +100,8 @@ __global__ __launch_bounds__(64) void align_sweep_kernel(const float *__restrict
             if (t < Tb) {
                 const double lz = (double)cl[k];
                 const double eb = (double)cb[k] - lz;
-                const double in1 = al_shr1(a[PPL - 1]);
-                const double in2 = PPL == 1 ? al_shr1(in1) : in1;      // s-2 of the lane's first label position
+                const double in1 = lat_shr1(a[PPL - 1]);
+                const double in2 = PPL == 1 ? lat_shr1(in1) : in1;      // s-2 of the lane's first label position
                 unsigned bits[NWORD];
 #pragma unroll
                 for (int w = 0; w < NWORD; ++w) bits[w] = 0;
@@ -190,8 +153,8 @@ __global__ __launch_bounds__(64) void align_sweep_kernel(const float *__restrict
         if (j == (s1 & (PPL - 1))) m1 = a[j];
         if (s2 >= 0 && j == (s2 & (PPL - 1))) m2 = a[j];
     }
-    const double v1 = al_readlane(m1, s1 / PPL);
-    const double v2 = s2 >= 0 ? al_readlane(m2, s2 / PPL) : NEG;
+    const double v1 = lat_readlane(m1, s1 / PPL);
+    const double v2 = s2 >= 0 ? lat_readlane(m2, s2 / PPL) : NEG;
     int end = s1;
     double sc = v1;
     if (v2 > v1) { end = s2; sc = v2; }
@@ -271,8 +234,6 @@ __global__ __launch_bounds__(64) void align_trace_kernel(int T, int B, int V, co
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
-static inline size_t al_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline int al_ppl(int S) { return S <= 64 ? 1 : S <= 128 ? 2 : S <= 256 ? 4 : S <= 512 ? 8 : S <= 1024 ? 16 : 32; }
 struct AlLayout {
     size_t lse, end, bp, total;
     int ppl, tg;
@@ -280,13 +241,13 @@ struct AlLayout {
 static inline AlLayout al_layout(int T, int B, int max_label_len)
 {
     AlLayout m;
-    m.ppl = al_ppl(2 * max_label_len + 1);
+    m.ppl = lat_ppl(2 * max_label_len + 1);
     const int jw = m.ppl < 16 ? m.ppl : 16, nword = (m.ppl + 15) / 16, tpw = 16 / jw;
     m.tg = (T + tpw - 1) / tpw;
     size_t o = 0;
-    m.lse = o; o += al_align256((size_t)T * B * sizeof(float));
-    m.end = o; o += al_align256((size_t)B * sizeof(int));
-    m.bp = o; o += al_align256((size_t)B * m.tg * nword * 64 * sizeof(unsigned));
+    m.lse = o; o += lc_align256((size_t)T * B * sizeof(float));
+    m.end = o; o += lc_align256((size_t)B * sizeof(int));
+    m.bp = o; o += lc_align256((size_t)B * m.tg * nword * 64 * sizeof(unsigned));
     m.total = o;
     return m;
 }
@@ -321,7 +282,7 @@ extern "C" int lc_ctc_align(const float *logits, int T, int B, int V, const int 
     unsigned *bp = (unsigned *)(w + m.bp);
     const int phases = g_align_phases;
     if (phases & 1) {
-        hipLaunchKernelGGL(align_lse_kernel, dim3(lc_cdiv((long long)T * B, 4)), dim3(256), 0, s, logits, T, B, V, seq_len,
+        hipLaunchKernelGGL(lat_lse_kernel, dim3(lc_cdiv((long long)T * B, 4)), dim3(256), 0, s, logits, T, B, V, seq_len,
                            lse);
         LC_CHECK_LAUNCH("ctc_align_lse");
     }

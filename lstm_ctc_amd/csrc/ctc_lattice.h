@@ -1,33 +1,63 @@
-// ctc_lattice.h — the device helpers of the double-cell log2-domain CTC lattices (ctc_window.hip, ctc_delay.hip; DESIGN.md
-// section 3.8): "log zero" is -inf itself, a cell is a double, the log-sum-exp of a cell's predecessors runs on the fp32
-// exp2 / log2 pipes relative to their maximum.
+// ctc_lattice.h — what the double-cell log2-domain CTC lattices share (ctc_lattice.hip: windowed and delay-penalised CTC,
+// ctc_align.hip: forced alignment; DESIGN.md sections 3.6, 3.8): the per-frame log-sum-exp kernel, -inf as "log zero", the
+// log-sum-exp of a cell's predecessors on the fp32 exp2 / log2 pipes relative to their maximum, the DPP neighbour shift.
 #pragma once
 #include "common.h"
 #include <float.h>
+#include <math.h>
 
-__device__ __forceinline__ double cw_neg_inf() { return __longlong_as_double(0xfff0000000000000ull); }
-// log2(2^a + 2^b [+ 2^c]); -inf operands are "log zero", all of them -inf gives -inf (see ctc_window.hip's header)
-__device__ __forceinline__ double cw_lse2(double a, double b)
+#define LAT_LOG2E 1.4426950408889634f
+#define LAT_LN2 0.6931471805599453
+
+namespace {
+
+// one wave per live frame (t, b): lse[t, b] = log sum_k exp(logits[t, b, k]), fp32.  Grid: ceil(T * B / 4) blocks of 256.
+__global__ __launch_bounds__(256) void lat_lse_kernel(const float *__restrict__ logits, int T, int B, int V,
+                                                      const int *__restrict__ seq_len, float *__restrict__ lse)
+{
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (size_t)T * B) return;
+    const int t = (int)(row / B), b = (int)(row % B);
+    if (t >= seq_len[b]) return;                                  // never read
+    const float *x = logits + row * V;
+    float m = -INFINITY;
+    for (int k = lane; k < V; k += 64) m = fmaxf(m, x[k]);
+    m = lc_wave_max(m);
+    float s = 0.0f;
+    for (int k = lane; k < V; k += 64) s += __builtin_amdgcn_exp2f((x[k] - m) * LAT_LOG2E);
+    s = lc_wave_sum(s);
+    if (lane == 0) lse[row] = m + __builtin_amdgcn_logf(s) * (float)LAT_LN2;
+}
+
+__device__ __forceinline__ double lat_neg_inf() { return __longlong_as_double(0xfff0000000000000ull); }
+// log2(2^a + 2^b [+ 2^c]); -inf operands are "log zero", all of them -inf gives -inf (see ctc_lattice.hip's header)
+__device__ __forceinline__ double lat_lse2(double a, double b)
 {
     const double m = fmax(fmax(a, b), -DBL_MAX);
     return m + (double)__builtin_amdgcn_logf(__builtin_amdgcn_exp2f((float)(a - m)) + __builtin_amdgcn_exp2f((float)(b - m)));
 }
-__device__ __forceinline__ double cw_lse3(double a, double b, double c)
+__device__ __forceinline__ double lat_lse3(double a, double b, double c)
 {
     const double m = fmax(fmax(fmax(a, b), c), -DBL_MAX);
     return m + (double)__builtin_amdgcn_logf(__builtin_amdgcn_exp2f((float)(a - m)) + __builtin_amdgcn_exp2f((float)(b - m)) +
                                              __builtin_amdgcn_exp2f((float)(c - m)));
 }
 // lane i receives x of lane i-1, lane 0 receives -inf (two 32-bit DPP wave_shr:1 moves)
-__device__ __forceinline__ double cw_shr1(double x)
+__device__ __forceinline__ double lat_shr1(double x)
 {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x138, 0xf, 0xf, false);
     const int hi = __builtin_amdgcn_update_dpp((int)0xfff00000, __double2hiint(x), 0x138, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double cw_readlane(double x, int lane)
+__device__ __forceinline__ double lat_readlane(double x, int lane)
 {
     const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
     return __hiloint2double(hi, lo);
 }
+
+// lattice positions per lane for a lattice of S = 2 L + 1 positions
+inline int lat_ppl(int S) { return S <= 64 ? 1 : S <= 128 ? 2 : S <= 256 ? 4 : S <= 512 ? 8 : S <= 1024 ? 16 : 32; }
+
+}  // namespace

@@ -1,0 +1,547 @@
+// ctc_lattice.hip — the two CTC criteria that sum over a constrained or re-weighted set of paths, on one lattice:
+//   * alignment-windowed CTC (lc_ctc_loss_windowed): the CTC loss and gradient summed only over the paths that keep every label
+//     inside a window of frames (Senior et al. 2015: windows around a forced alignment stop a unidirectional model emitting
+//     late).  DESIGN.md section 3.8.
+//   * delay-penalised CTC (lc_ctc_loss_delay, Kang et al. 2023): the CTC criterion over paths weighted by exp(-lambda * E(path)),
+//     E = sum over the labels of the frame at which the label's run starts, plus E's expectation under that tilted posterior
+//     (entry_sum: the "expected frame at which a label is entered", summed over the labels), with optional label windows.
+//     DESIGN.md section 3.10.
+// No reference counterpart.  lc_ctc_loss (ctc.hip) is not touched by this file.
+//
+// Contract (include/lstm_ctc_hip.h): lc_ctc_loss's, plus win_lo / win_hi parallel to the flat labels.  Label j may sit on
+// frame t only when win_lo[j] <= t <= win_hi[j]; blank positions are never constrained.
+//
+// Both entries run lat_launch: lse, [index], sweep, [grad<ENTRY> | entry], [fold] - four launches for the windowed loss (two
+// without a gradient).  No LDS atomics, no global atomics, every sum in a fixed order - the result is bit-identical from call
+// to call:
+//   1. lat_lse_kernel        (ctc_lattice.h) one wave per live frame (t, b): lse[t, b] = log sum_k exp(logits[t, b, k]), fp32.
+//   2. lat_index_kernel      (gradient only) one workgroup per utterance: the label indices ordered by (class, index), and per
+//                            class the first rank and the count.  Ranks come from counting, so the order is a pure function
+//                            of the labels.
+//   3. lat_sweep_kernel<PPL, DELAY>  one wave per (utterance, direction), 2B waves, no barrier.  ctc_align.hip's geometry: lane l
+//      holds the PPL consecutive lattice positions l * PPL .. l * PPL + PPL - 1, the s-1 / s-2 neighbours of its first position
+//      come by one DPP wave shift.  BOTH directions are the same forward recursion: direction 1 walks the frames backwards over
+//      the REVERSED lattice (position p stands for lattice position S - 1 - p; S is odd, so label positions stay odd and the
+//      "s-2 only between different labels" rule is symmetric), which yields beta INCLUDING the frame's own emission.  A cell
+//      is a DOUBLE in the log2 domain (v_exp_f32 / v_log_f32 are base 2), as in ctc_align.hip: the log-sum-exp of a cell's
+//      predecessors is m + log2(sum 2^(a_i - m)) with the differences rounded to fp32 and the exponentials and the logarithm
+//      on the fp32 pipes (a term far below the maximum has no weight, so its rounding does not matter), and m + ., + emission
+//      are double additions - a cell's error is a few fp32 ulps of a number below 2, whatever the cell's magnitude, and there
+//      is no re-centring and no offset to carry.  (fp32 cells re-centred on the row maximum were built first: the cells that
+//      carry the paths lie hundreds of bits below the best PREFIX when windows or a tight T force the path, and the
+//      gradient error reached the project's 1e-4 bar at T = 164.)  A cell's emission is the fp32 log-softmax
+//      (logits - lse) * log2(e).  "Log zero" is -inf itself: a masked cell (frame outside the label's window) is set to -inf
+//      by a select, and the log-sum-exp takes its maximum through fmax(m, -DBL_MAX), so that an all-dead neighbourhood gives
+//      -DBL_MAX + log2(0) = -inf and never -inf - -inf: a dead cell stays dead and no NaN can arise, also when every cell of
+//      a row is dead.  The rows go to the workspace.  Direction 0 finishes with log2 p = log-sum-exp of the two end cells
+//      and the loss, rounded once.
+//      DELAY (lc_ctc_loss_delay; the windowed instantiation carries none of it):
+//        * the arc weight w(t) = -lambda * log2(e) * t, formed and added in double, on every arc that ENTERS a label position
+//          (from s-1 or s-2) at frame t; "stay" arcs and arcs into blanks carry none.  Frame 0 carries none.
+//        * the backward sweep is still the forward recursion on the reversed lattice, but an arc's weight belongs to its
+//          TARGET in the original orientation, which the reverse walk sees as the arc's SOURCE: a move out of an odd (label)
+//          position of the previously processed row t + 1 carries w(t + 1).  (Out of an odd position p - 1 into the blank p,
+//          or out of the odd p - 2 into the odd p; the move p - 1 -> p into an odd p leaves a blank and carries nothing.)
+//        * the windows may be NULL (no constraint).
+//   4. lat_grad_kernel<ENTRY>  one wave per frame.  occupancy(t, s) = 2^(alpha + beta - emission - log2 p), the exponent formed
+//      in double; lane k sums the positions of class k, k + 64, ... in the order of lat_index_kernel's list, the blank's
+//      positions are summed lane by lane and then by the wave's DPP reduction.  grad = softmax - occupancy.  ENTRY also sums
+//      occupancy(t, s) * notyet(s), notyet(s) = L - (s + 1) / 2, per frame in double (each lane its positions in sequence,
+//      then a fixed butterfly) into the workspace; without a gradient lat_entry_kernel does the same from the two lattices
+//      alone.
+//   5. lat_fold_kernel       (entry_sum only) one wave per utterance folds its frame terms in a fixed order in double and rounds
+//      once.
+// The band (only positions whose window contains t are live) is NOT exploited: every position is computed on every frame.
+#include "common.h"
+#include "ctc_lattice.h"
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+
+#define LAT_LOG2E_D 1.4426950408889634
+#define LAT_OK 0
+#define LAT_ZERO 1                       // skipped utterance: loss 0, gradient rows zeros, entry_sum 0
+#define LAT_NOPATH 2                     // loss +inf, gradient = softmax on the live frames, entry_sum 0
+#define LAT_NAN 3                        // bad label: loss NaN, gradient rows zeros, entry_sum NaN
+
+namespace {
+
+// ------------------------------------------------------------------------------------------ 2. class -> positions lists
+// order[b][r] = index of the label of rank r in (class, index) order; first[b][k] / cnt[b][k] = rank of class k's first
+// label / number of its labels.  Labels outside [0, V) take part in the ranking but belong to no class (the sweep gives such
+// an utterance a NaN loss and nothing reads its lists); every rank is below L, so nothing is written out of bounds.
+__global__ __launch_bounds__(256) void lat_index_kernel(int V, const int *__restrict__ labels, const int *__restrict__ offs,
+                                                        int maxL, int pitch, int *__restrict__ order,
+                                                        int *__restrict__ first, int *__restrict__ cnt)
+{
+    __shared__ int lab[1024];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int off = offs[b];
+    int L = offs[b + 1] - off;
+    if (L < 0 || L > maxL) L = 0;
+    for (int i = tid; i < L; i += 256) lab[i] = labels[off + i];
+    __syncthreads();
+    int *ord = order + (size_t)b * pitch;
+    for (int i = tid; i < L; i += 256) {
+        const int me = lab[i];
+        int rank = 0;
+        for (int j = 0; j < L; ++j) {
+            const int o = lab[j];
+            rank += (o < me || (o == me && j < i)) ? 1 : 0;
+        }
+        ord[rank] = i;
+    }
+    for (int k = tid; k < V; k += 256) {
+        int lt = 0, eq = 0;
+        for (int j = 0; j < L; ++j) {
+            const int o = lab[j];
+            lt += o < k ? 1 : 0;
+            eq += o == k ? 1 : 0;
+        }
+        first[(size_t)b * V + k] = lt;
+        cnt[(size_t)b * V + k] = eq;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ 3. alpha / beta sweeps
+// DELAY = false: win_lo / win_hi are not NULL (the host checks) and lambda is not read.
+template <int PPL, bool DELAY>
+__global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__ logits, int T, int B, int V,
+                                                       const int *__restrict__ labels, const int *__restrict__ offs,
+                                                       const int *__restrict__ seq_len, int maxL,
+                                                       const int *__restrict__ win_lo, const int *__restrict__ win_hi,
+                                                       float lambda, const float *__restrict__ lse,
+                                                       double *__restrict__ alpha, double *__restrict__ beta, int srow,
+                                                       int want_beta, float *__restrict__ loss,
+                                                       double *__restrict__ lp2, int *__restrict__ status)
+{
+    constexpr int K = PPL <= 4 ? 8 : 32 / PPL;            // frames fetched ahead as one chunk: 8, 8, 8, 4, 2, 1
+    constexpr int NG = PPL == 1 ? 1 : PPL / 2;            // label positions (gathers, windows) per lane
+    const int b = blockIdx.x >> 1, dir = blockIdx.x & 1, lane = threadIdx.x;
+    if (dir == 1 && !want_beta) return;
+    const int Tb = min(max(seq_len[b], 0), T);
+    const int off = offs[b], L = offs[b + 1] - off, S = 2 * L + 1;
+    const int blank = V - 1;
+    const double NEG = lat_neg_inf();
+    if (Tb == 0 || L > Tb) {                              // lc_ctc_loss: the utterance is skipped, loss 0, gradient 0
+        if (lane == 0 && dir == 0) { loss[b] = 0.0f; lp2[b] = 0.0; status[b] = LAT_ZERO; }
+        return;
+    }
+    {   // a label outside [0, V-1) (or a label count the workspace was not sized for): NaN loss, zero gradient, and the labels
+        // never index anything
+        int bad = (L < 0 || L > maxL) ? 1 : 0;
+        if (!bad)
+            for (int i = lane; i < L; i += 64) {
+                const int lab = labels[off + i];
+                bad |= (lab < 0 || lab >= blank) ? 1 : 0;
+            }
+        if (__builtin_amdgcn_ballot_w64(bad != 0) != 0) {
+            if (lane == 0 && dir == 0) { loss[b] = __int_as_float(0x7fc00000); lp2[b] = 0.0; status[b] = LAT_NAN; }
+            return;
+        }
+    }
+    // per position: is it inside the lattice, may it be entered from two positions back; per label position: class, window
+    unsigned valid = 0, allow2 = 0;
+    int gsym[NG], wlo[NG], whi[NG];
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+        const int p = lane * PPL + j;
+        if (p < S) valid |= 1u << j;
+        if (PPL == 1 || (j & 1)) {
+            int sym = blank, lo = 0, hi = INT_MAX;
+            if ((p & 1) && p < S) {
+                const int i = dir ? L - 1 - (p >> 1) : (p >> 1);          // the label this position stands for
+                sym = labels[off + i];
+                if (!DELAY || win_lo) {
+                    lo = win_lo[off + i];
+                    hi = win_hi[off + i];
+                }
+                if (p >= 3 && sym != labels[off + (dir ? i + 1 : i - 1)]) allow2 |= 1u << j;
+            }
+            gsym[PPL == 1 ? 0 : j >> 1] = sym;
+            wlo[PPL == 1 ? 0 : j >> 1] = lo;
+            whi[PPL == 1 ? 0 : j >> 1] = hi;
+        }
+    }
+    double a[PPL];
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) a[j] = NEG;
+    if (lane == 0) a[0] = 0.0;                            // "before the first frame": it reaches positions 0 (stay) and 1
+    const double wl = DELAY ? -(double)lambda * LAT_LOG2E_D : 0.0;       // w(t) = wl * t
+
+    float cg[K][NG], cb[K], cl[K], ng[K][NG], nb[K], nl[K];
+    auto fetch = [&](int k0, float (&g)[K][NG], float (&gb)[K], float (&gl)[K]) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int kk = min(k0 + k, Tb - 1);
+            const int t = dir ? Tb - 1 - kk : kk;
+            const size_t row = (size_t)t * B + b;
+            const float *x = logits + row * V;
+#pragma unroll
+            for (int g_ = 0; g_ < NG; ++g_) g[k][g_] = x[gsym[g_]];
+            gb[k] = x[blank];
+            gl[k] = lse[row];
+        }
+    };
+    fetch(0, cg, cb, cl);
+    double *rows = (dir ? beta : alpha) + (size_t)b * T * srow;
+    for (int k0 = 0; k0 < Tb; k0 += K) {
+        fetch(k0 + K, ng, nb, nl);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int kk = k0 + k;
+            if (kk < Tb) {
+                const int t = dir ? Tb - 1 - kk : kk;
+                const float lz = cl[k];
+                const float eb = (cb[k] - lz) * LAT_LOG2E;
+                // DELAY, forward: the arcs into a label position of this row carry w(t).  Backward (reversed lattice): the arcs
+                // out of a label position of the row before, frame t + 1, carry w(t + 1) - that is p-1 -> p for an even p and
+                // p-2 -> p for an odd p.  An arc p-2 -> p joins two label positions in either direction.
+                const double w = DELAY ? wl * (double)(dir ? t + 1 : t) : 0.0;
+                const double w1odd = dir ? 0.0 : w, w1even = dir ? w : 0.0;
+                const double in1 = lat_shr1(a[PPL - 1]);
+                const double in2 = PPL == 1 ? lat_shr1(in1) : in1;           // s-2 of the lane's first label position
+#pragma unroll
+                for (int j = PPL - 1; j >= 0; --j) {                         // descending: a[j-1], a[j-2] are the old frame's
+                    const double p1 = j >= 1 ? a[j - 1] : in1;
+                    const int g_ = PPL == 1 ? 0 : j >> 1;
+                    double v;
+                    float e = eb;
+                    bool live = (valid >> j & 1u) != 0;
+                    if (PPL == 1) {
+                        const double p2 = (allow2 & 1u) ? (DELAY ? in2 + w : in2) : NEG;
+                        v = lat_lse3(a[0], DELAY ? p1 + ((lane & 1) ? w1odd : w1even) : p1, p2);
+                        if (lane & 1) e = (cg[k][0] - lz) * LAT_LOG2E;
+                        live = live && t >= wlo[0] && t <= whi[0];           // blank lanes: lo = 0, hi = INT_MAX
+                    } else if (j & 1) {
+                        double p2 = j >= 2 ? a[j - 2] : in2;
+                        p2 = (allow2 >> j & 1u) ? (DELAY ? p2 + w : p2) : NEG;
+                        v = lat_lse3(a[j], DELAY ? p1 + w1odd : p1, p2);
+                        e = (cg[k][g_] - lz) * LAT_LOG2E;
+                        live = live && t >= wlo[g_] && t <= whi[g_];
+                    } else {
+                        v = lat_lse2(a[j], DELAY ? p1 + w1even : p1);        // blanks are never entered from s-2
+                    }
+                    a[j] = live ? v + (double)e : NEG;
+                }
+                // the row
+                double *dst = rows + (size_t)t * srow;
+                if constexpr (PPL == 1) {
+                    dst[lane] = a[0];                                        // srow >= 64
+                } else {
+#pragma unroll
+                    for (int c = 0; c < PPL / 2; ++c) {
+                        const int p0 = lane * PPL + 2 * c;                   // srow is a multiple of 64: both or none
+                        if (p0 < srow) *(double2 *)(dst + p0) = make_double2(a[2 * c], a[2 * c + 1]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int g_ = 0; g_ < NG; ++g_) cg[k][g_] = ng[k][g_];
+            cb[k] = nb[k];
+            cl[k] = nl[k];
+        }
+    }
+    if (dir == 1) return;
+    // log2 of the (weighted) path sum: the path ends in S-1 or S-2
+    const int s1 = S - 1, s2 = S - 2;
+    double m1 = NEG, m2 = NEG;
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+        if (j == (s1 & (PPL - 1))) m1 = a[j];
+        if (s2 >= 0 && j == (s2 & (PPL - 1))) m2 = a[j];
+    }
+    const double v1 = lat_readlane(m1, s1 / PPL);
+    const double v2 = s2 >= 0 ? lat_readlane(m2, s2 / PPL) : NEG;
+    if (lane == 0) {
+        const double hi = fmax(v1, v2), lo = fmin(v1, v2);
+        if (!(hi > NEG)) {                                                   // no surviving path
+            loss[b] = INFINITY; lp2[b] = 0.0; status[b] = LAT_NOPATH;
+        } else {
+            const double lp = hi + (double)__builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f((float)(lo - hi)));
+            loss[b] = (float)(0.0 - lp * LAT_LN2);
+            lp2[b] = lp; status[b] = LAT_OK;
+        }
+    }
+}
+
+// the wave's sum of a double in a fixed order (xor butterfly), the same value in every lane
+__device__ __forceinline__ double lat_wave_sum_d(double x)
+{
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) {
+        const int lo = __shfl_xor(__double2loint(x), mask, 64), hi = __shfl_xor(__double2hiint(x), mask, 64);
+        x += __hiloint2double(hi, lo);
+    }
+    return x;
+}
+
+// ------------------------------------------------------------------------------------------ 4. gradient (+ entry terms)
+template <bool ENTRY>
+__global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__ logits, int T, int B, int V,
+                                                       const int *__restrict__ offs, const int *__restrict__ seq_len,
+                                                       const float *__restrict__ lse, const double *__restrict__ alpha,
+                                                       const double *__restrict__ beta, int srow,
+                                                       const double *__restrict__ lp2, const int *__restrict__ status,
+                                                       const int *__restrict__ order, int pitch,
+                                                       const int *__restrict__ first, const int *__restrict__ cnt,
+                                                       float *__restrict__ grad, double *__restrict__ fterm)
+{
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (size_t)T * B) return;
+    const int t = (int)(row / B), b = (int)(row % B);
+    const int Tb = min(max(seq_len[b], 0), T);
+    const int st = status[b];
+    const float *x = logits + row * V;
+    float *g = grad + row * V;
+    if (t >= Tb || st == LAT_ZERO || st == LAT_NAN) {                        // wave-uniform
+        for (int k = lane; k < V; k += 64) g[k] = 0.0f;
+        return;
+    }
+    const float lz = lse[row];
+    if (st == LAT_NOPATH) {
+        for (int k = lane; k < V; k += 64) g[k] = __builtin_amdgcn_exp2f((x[k] - lz) * LAT_LOG2E);
+        return;
+    }
+    const int L = offs[b + 1] - offs[b], S = 2 * L + 1;
+    const size_t bt = (size_t)b * T + t;
+    const double *A = alpha + bt * srow, *Bt = beta + bt * srow;
+    const double lp = lp2[b];
+    const int blank = V - 1;
+    double eacc = 0.0;                                                       // this lane's sum of occupancy * notyet
+    // the blank: positions 0, 2, .., 2L, lane l takes 2l, 2l + 128, ... in sequence, then the wave's fixed reduction
+    const float eb = (x[blank] - lz) * LAT_LOG2E;
+    {
+        const double c = (double)eb + lp;
+        float acc = 0.0f;
+        for (int s = 2 * lane; s < S; s += 128) {
+            const float o = __builtin_amdgcn_exp2f((float)((A[s] + Bt[S - 1 - s]) - c));
+            acc += o;
+            if (ENTRY) eacc += (double)o * (double)(L - (s >> 1));
+        }
+        acc = lc_wave_sum(acc);
+        if (lane == 0) g[blank] = __builtin_amdgcn_exp2f(eb) - acc;
+    }
+    // the labels: lane k sums the positions of class k in the order of the utterance's list
+    const int *ord = order + (size_t)b * pitch;
+    const int *fr = first + (size_t)b * V, *cn = cnt + (size_t)b * V;
+    for (int k = lane; k < blank; k += 64) {
+        const float e = (x[k] - lz) * LAT_LOG2E;
+        const double c = (double)e + lp;
+        const int r0 = fr[k], n = cn[k];
+        float acc = 0.0f;
+        for (int r = 0; r < n; ++r) {
+            const int i = ord[r0 + r], s = 2 * i + 1;
+            const float o = __builtin_amdgcn_exp2f((float)((A[s] + Bt[S - 1 - s]) - c));
+            acc += o;
+            if (ENTRY) eacc += (double)o * (double)(L - 1 - i);
+        }
+        g[k] = __builtin_amdgcn_exp2f(e) - acc;
+    }
+    if (ENTRY) {
+        eacc = lat_wave_sum_d(eacc);
+        if (lane == 0) fterm[bt] = eacc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ 4'. entry terms alone
+// One wave per live frame of an utterance with a path: sum_s occupancy(t, s) * notyet(s), lane l takes s = l, l + 64, ...
+__global__ __launch_bounds__(256) void lat_entry_kernel(const float *__restrict__ logits, int T, int B, int V,
+                                                        const int *__restrict__ labels, const int *__restrict__ offs,
+                                                        const int *__restrict__ seq_len, const float *__restrict__ lse,
+                                                        const double *__restrict__ alpha, const double *__restrict__ beta,
+                                                        int srow, const double *__restrict__ lp2,
+                                                        const int *__restrict__ status, double *__restrict__ fterm)
+{
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (size_t)T * B) return;
+    const int t = (int)(row / B), b = (int)(row % B);
+    const int Tb = min(max(seq_len[b], 0), T);
+    if (t >= Tb || status[b] != LAT_OK) return;                              // wave-uniform; the fold never reads these
+    const float *x = logits + row * V;
+    const float lz = lse[row];
+    const int off = offs[b], L = offs[b + 1] - off, S = 2 * L + 1;
+    const size_t bt = (size_t)b * T + t;
+    const double *A = alpha + bt * srow, *Bt = beta + bt * srow;
+    const double lp = lp2[b];
+    double eacc = 0.0;
+    for (int s = lane; s < S; s += 64) {
+        const int sym = (s & 1) ? labels[off + (s >> 1)] : V - 1;            // status OK: every label lies in [0, V-1)
+        const float e = (x[sym] - lz) * LAT_LOG2E;
+        const float o = __builtin_amdgcn_exp2f((float)((A[s] + Bt[S - 1 - s]) - ((double)e + lp)));
+        eacc += (double)o * (double)(L - ((s + 1) >> 1));
+    }
+    eacc = lat_wave_sum_d(eacc);
+    if (lane == 0) fterm[bt] = eacc;
+}
+
+// ------------------------------------------------------------------------------------------ 5. per-utterance fold
+// One wave per utterance: lane l sums the terms of frames l, l + 64, ... in sequence, then the fixed butterfly; rounded once.
+__global__ __launch_bounds__(64) void lat_fold_kernel(const double *__restrict__ fterm, int T, const int *__restrict__ seq_len,
+                                                      const int *__restrict__ status, float *__restrict__ entry_sum)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int st = status[b];
+    if (st != LAT_OK) {
+        if (lane == 0) entry_sum[b] = st == LAT_NAN ? __int_as_float(0x7fc00000) : 0.0f;
+        return;
+    }
+    const int Tb = min(max(seq_len[b], 0), T);
+    const double *f = fterm + (size_t)b * T;
+    double acc = 0.0;
+    for (int t = lane; t < Tb; t += 64) acc += f[t];
+    acc = lat_wave_sum_d(acc);
+    if (lane == 0) entry_sum[b] = (float)acc;
+}
+
+// ------------------------------------------------------------------------------------------ host
+// the workspace: slabs in this order; only the delay entry has the frame terms
+struct LatLayout {
+    size_t lse, status, lp2, order, first, cnt, fterm, alpha, beta, total;
+    int ppl, srow, pitch;
+};
+inline LatLayout lat_layout(int T, int B, int V, int max_label_len, bool with_fterm)
+{
+    LatLayout m;
+    const int S = 2 * max_label_len + 1;
+    m.ppl = lat_ppl(S);
+    m.srow = (S + 63) / 64 * 64;                         // <= 64 * ppl
+    m.pitch = max_label_len > 0 ? max_label_len : 1;
+    const size_t TB = (size_t)T * B;
+    size_t o = 0;
+    m.lse = o; o += lc_align256(TB * sizeof(float));
+    m.status = o; o += lc_align256((size_t)B * sizeof(int));
+    m.lp2 = o; o += lc_align256((size_t)B * sizeof(double));
+    m.order = o; o += lc_align256((size_t)B * m.pitch * sizeof(int));
+    m.first = o; o += lc_align256((size_t)B * V * sizeof(int));
+    m.cnt = o; o += lc_align256((size_t)B * V * sizeof(int));
+    m.fterm = o; o += with_fterm ? lc_align256(TB * sizeof(double)) : 0;
+    m.alpha = o; o += lc_align256(TB * m.srow * sizeof(double));
+    m.beta = o; o += lc_align256(TB * m.srow * sizeof(double));
+    m.total = o;
+    return m;
+}
+inline size_t lat_workspace_bytes(int T, int B, int V, int max_label_len, bool with_fterm)
+{
+    if (T <= 0 || B <= 0 || V < 2 || max_label_len < 0 || max_label_len > 1023) return 0;
+    return lat_layout(T, B, V, max_label_len, with_fterm).total;
+}
+
+// what tells the two entries apart on the host: the name in front of an error, the tags of the launches
+struct LatEntry {
+    bool delay;
+    const char *name, *lse, *index, *sweep, *grad, *entry, *fold;
+};
+const LatEntry LAT_WINDOW = {false, "lc_ctc_loss_windowed", "ctc_window_lse", "ctc_window_index", "ctc_window_sweep",
+                             "ctc_window_grad", "ctc_window_entry", "ctc_window_fold"};
+const LatEntry LAT_DELAY = {true, "lc_ctc_loss_delay", "ctc_delay_lse", "ctc_delay_index", "ctc_delay_sweep",
+                            "ctc_delay_grad", "ctc_delay_entry", "ctc_delay_fold"};
+
+// The windowed entry comes with windows, delay_penalty 0 and no entry_sum.
+int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+               const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi, float delay_penalty, float *loss,
+               float *entry_sum, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream)
+{
+    LC_CHECK_ARG(logits && labels && label_offsets && seq_len && loss && workspace && (e.delay || (win_lo && win_hi)),
+                 "%s: null pointer", e.name);
+    LC_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr), "%s: win_lo and win_hi go together (both or none)", e.name);
+    LC_CHECK_ARG(T > 0 && B > 0 && V >= 2 && max_label_len >= 0, "%s: bad shape T=%d B=%d V=%d L=%d", e.name, T, B, V,
+                 max_label_len);
+    LC_CHECK_ARG(max_label_len <= 1023, "%s: label length %d exceeds the supported maximum 1023", e.name, max_label_len);
+    LC_CHECK_ARG(isfinite(delay_penalty), "%s: delay_penalty must be finite, got %g", e.name, (double)delay_penalty);
+    LC_CHECK_ARG((long long)B * 2 <= 0x7fffffffLL && ((long long)T * B + 3) / 4 <= 0x7fffffffLL,
+                 "%s: T * B = %lld is beyond the launch grid", e.name, (long long)T * B);
+    const LatLayout m = lat_layout(T, B, V, max_label_len, e.delay);
+    if (workspace_bytes < m.total) {
+        lc_set_error("%s: workspace too small (%zu < %zu)", e.name, workspace_bytes, m.total);
+        return LC_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char *w = (char *)workspace;
+    float *lse = (float *)(w + m.lse);
+    int *status = (int *)(w + m.status);
+    double *lp2 = (double *)(w + m.lp2);
+    int *order = (int *)(w + m.order), *first = (int *)(w + m.first), *cnt = (int *)(w + m.cnt);
+    double *fterm = (double *)(w + m.fterm);             // only with entry_sum, which only the delay entry has
+    double *alpha = (double *)(w + m.alpha), *beta = (double *)(w + m.beta);
+    const unsigned frame_blocks = (unsigned)(((long long)T * B + 3) / 4);
+    hipLaunchKernelGGL(lat_lse_kernel, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, seq_len, lse);
+    LC_CHECK_LAUNCH(e.lse);
+    if (grad) {
+        hipLaunchKernelGGL(lat_index_kernel, dim3(B), dim3(256), 0, s, V, labels, label_offsets, max_label_len, m.pitch, order,
+                           first, cnt);
+        LC_CHECK_LAUNCH(e.index);
+    }
+#define LC_LAT(PPL, DELAY)                                                                                              \
+    hipLaunchKernelGGL((lat_sweep_kernel<PPL, DELAY>), dim3(2 * B), dim3(64), 0, s, logits, T, B, V, labels, label_offsets, \
+                       seq_len, max_label_len, win_lo, win_hi, delay_penalty, lse, alpha, beta, m.srow,                 \
+                       (grad || entry_sum) ? 1 : 0, loss, lp2, status)
+    switch (e.delay ? -m.ppl : m.ppl) {                  // the sign picks the DELAY instantiations
+    case 1: LC_LAT(1, false); break;
+    case 2: LC_LAT(2, false); break;
+    case 4: LC_LAT(4, false); break;
+    case 8: LC_LAT(8, false); break;
+    case 16: LC_LAT(16, false); break;
+    case 32: LC_LAT(32, false); break;
+    case -1: LC_LAT(1, true); break;
+    case -2: LC_LAT(2, true); break;
+    case -4: LC_LAT(4, true); break;
+    case -8: LC_LAT(8, true); break;
+    case -16: LC_LAT(16, true); break;
+    default: LC_LAT(32, true); break;
+    }
+#undef LC_LAT
+    LC_CHECK_LAUNCH(e.sweep);
+    if (grad && entry_sum) {
+        hipLaunchKernelGGL(lat_grad_kernel<true>, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, label_offsets, seq_len,
+                           lse, alpha, beta, m.srow, lp2, status, order, m.pitch, first, cnt, grad, fterm);
+        LC_CHECK_LAUNCH(e.grad);
+    } else if (grad) {
+        hipLaunchKernelGGL(lat_grad_kernel<false>, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, label_offsets, seq_len,
+                           lse, alpha, beta, m.srow, lp2, status, order, m.pitch, first, cnt, grad, fterm);
+        LC_CHECK_LAUNCH(e.grad);
+    } else if (entry_sum) {
+        hipLaunchKernelGGL(lat_entry_kernel, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, labels, label_offsets,
+                           seq_len, lse, alpha, beta, m.srow, lp2, status, fterm);
+        LC_CHECK_LAUNCH(e.entry);
+    }
+    if (entry_sum) {
+        hipLaunchKernelGGL(lat_fold_kernel, dim3(B), dim3(64), 0, s, fterm, T, seq_len, status, entry_sum);
+        LC_CHECK_LAUNCH(e.fold);
+    }
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t lc_ctc_window_workspace_bytes(int T, int B, int V, int max_label_len)
+{
+    return lat_workspace_bytes(T, B, V, max_label_len, false);
+}
+
+extern "C" size_t lc_ctc_delay_workspace_bytes(int T, int B, int V, int max_label_len)
+{
+    return lat_workspace_bytes(T, B, V, max_label_len, true);
+}
+
+extern "C" int lc_ctc_loss_windowed(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                                    const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
+                                    float *loss, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream)
+{
+    return lat_launch(LAT_WINDOW, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi, 0.0f, loss,
+                      nullptr, grad, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lc_ctc_loss_delay(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                                 const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
+                                 float delay_penalty, float *loss, float *entry_sum, float *grad, void *workspace,
+                                 size_t workspace_bytes, lc_stream_t stream)
+{
+    return lat_launch(LAT_DELAY, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi, delay_penalty,
+                      loss, entry_sum, grad, workspace, workspace_bytes, stream);
+}

@@ -205,22 +205,7 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------ 1b. any row width
-// One pass of a wave over a row of V elements, as xent.hip's xe_walk_row: `head` = 0 .. 3 elements up to the first 16-byte
-// boundary as dwords, the body in 16-byte accesses, the rest as dwords.  A lane's indices rise in the order it visits them.
-template <bool VEC, class F1, class F4>
-__device__ __forceinline__ void kd_walk_row(int lane, int V, int head, F1 f1, F4 f4)
-{
-    if (!VEC) {
-        for (int e = lane; e < V; e += 64) f1(e);
-        return;
-    }
-    if (lane < head) f1(lane);
-    const int nq = (V - head) >> 2;
-    for (int q = lane; q < nq; q += 64) f4(head + 4 * q);
-    const int rest = head + 4 * nq;
-    if (lane < V - rest) f1(rest + lane);
-}
-
+// rg_walk_row (row_group.h) is one pass of a wave over a row.
 template <bool VEC>
 __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ logits, const float *__restrict__ teacher,
                                                       int T, int B, int V, const int *__restrict__ seq_len,
@@ -243,7 +228,7 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
         if (!scored) {                                                       // wave-uniform
             if (lane == 0) terms[bt] = make_int2(0, 0);
             if (gr && !acc)
-                kd_walk_row<VEC>(lane, V, head, [&](int e) { gr[e] = 0.0f; },
+                rg_walk_row<VEC>(lane, V, head, [&](int e) { gr[e] = 0.0f; },
                                  [&](int e) { *(float4 *)(gr + e) = make_float4(0.f, 0.f, 0.f, 0.f); });
             continue;
         }
@@ -254,7 +239,7 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
             if (u > ms || (cs == 0x7fffffff && u == ms)) { ms = u; cs = e; }
             if (v > mz || (cz == 0x7fffffff && v == mz)) { mz = v; cz = e; }
         };
-        kd_walk_row<VEC>(lane, V, head, [&](int e) { top(sr[e], zr[e], e); },
+        rg_walk_row<VEC>(lane, V, head, [&](int e) { top(sr[e], zr[e], e); },
                          [&](int e) {
                              const float4 u = *(const float4 *)(sr + e), v = *(const float4 *)(zr + e);
                              top(u.x, v.x, e); top(u.y, v.y, e + 1); top(u.z, v.z, e + 2); top(u.w, v.w, e + 3);
@@ -265,7 +250,7 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
         const bool same = rg_min<64>(lms == ms ? cs : 0x7fffffff) == rg_min<64>(lmz == mz ? cz : 0x7fffffff);
         // pass 2: the three sums, per lane in the order of its visits, then over the lanes
         float sp = 0.0f, sq = 0.0f, ka = 0.0f;
-        kd_walk_row<VEC>(lane, V, head,
+        rg_walk_row<VEC>(lane, V, head,
                          [&](int e) {
                              float u = sr[e], v = zr[e];
                              kd_element(u, v, ms, mz, c, sp, sq, ka);
@@ -292,7 +277,7 @@ __global__ __launch_bounds__(256) void kd_wide_kernel(const float *__restrict__ 
                 const float d = __builtin_amdgcn_exp2f((v - mz) * c) * iq - __builtin_amdgcn_exp2f((u - ms) * c) * ip;
                 return acc ? d + o : d;
             };
-            kd_walk_row<VEC>(lane, V, head,
+            rg_walk_row<VEC>(lane, V, head,
                              [&](int e) {
                                  float o = 0.0f, u = 0.0f, v = 0.0f;
                                  if (good) { u = sr[e]; v = zr[e]; if (acc) o = gr[e]; }
@@ -323,7 +308,7 @@ __global__ __launch_bounds__(256) void kd_fold_kernel(const int2 *__restrict__ t
 extern "C" size_t lc_kd_workspace_bytes(int T, int B, int V)
 {
     if (T <= 0 || B <= 0 || V < 2) return 0;
-    return rg_align256((size_t)T * B * sizeof(int2));              // per frame: its term (float) and a flag word
+    return lc_align256((size_t)T * B * sizeof(int2));              // per frame: its term (float) and a flag word
 }
 
 extern "C" int lc_kd_loss(const float *logits, const float *teacher, int T, int B, int V, const int *seq_len,

@@ -1,5 +1,7 @@
-// row_group.h — what the two-launch frame criteria that pair two rows per frame share (kd.hip, consistency.hip): reductions over
-// a group of lanes that holds one frame, the grid-stride walk over the frames, and the fixed-order fold of the per-frame terms.
+// row_group.h — what the two-launch frame criteria share (xent.hip: one row per frame; kd.hip, consistency.hip: two rows per
+// frame): reductions over a group of lanes that holds one frame, the grid-stride walk over the frames, a wave's pass over a row
+// of any width, and the fixed-order fold of the per-frame terms.  The flag word's second bit is "the argmax is the target"
+// for xent.hip and "the two argmaxes agree" for the other two.
 #pragma once
 #include "common.h"
 
@@ -42,7 +44,8 @@ template <int G> __device__ __forceinline__ int rg_min(int v)
     return v;
 }
 
-// The waves walk the frames f = t * B + b with a grid stride; (t, b) are carried along by additions.
+// What a frame is: its utterance and its time step.  The waves walk the frames f = t * B + b with a grid stride; (t, b) are
+// carried along by additions (one division pair per wave at the start, none per frame).
 struct RgWalk {
     int t0, b0, st, sb;
     __device__ __forceinline__ RgWalk(int first, int stride, int B) : t0(first / B), b0(first % B), st(stride / B), sb(stride % B) {}
@@ -53,6 +56,24 @@ struct RgWalk {
         if (b0 >= B) { b0 -= B; ++t0; }
     }
 };
+
+// ---- one pass of a wave over a row of V elements.  VEC (16-byte aligned buffers, any V): the row starts `head` = 0 .. 3
+// elements short of a 16-byte boundary; lanes 0 .. head - 1 take those as dwords, the body goes in 16-byte accesses, the last
+// (V - head) % 4 elements as dwords again.  A lane's indices rise in the order it visits them.  f1(e): element e; f4(e):
+// elements e .. e + 3, 16-byte aligned.
+template <bool VEC, class F1, class F4>
+__device__ __forceinline__ void rg_walk_row(int lane, int V, int head, F1 f1, F4 f4)
+{
+    if (!VEC) {
+        for (int e = lane; e < V; e += 64) f1(e);
+        return;
+    }
+    if (lane < head) f1(lane);
+    const int nq = (V - head) >> 2;
+    for (int q = lane; q < nq; q += 64) f4(head + 4 * q);
+    const int rest = head + 4 * nq;
+    if (lane < V - rest) f1(rest + lane);
+}
 
 // ---- the fold: the body of a kernel of 256 threads, one workgroup per utterance (or pair) b = blockIdx.x.  terms [B,T]: a
 // frame's term (float bits) and its flag word.  The terms are added in a FIXED order in double and rounded once.
@@ -95,7 +116,5 @@ __device__ __forceinline__ void rg_fold(const int2 *__restrict__ terms, int T, f
         agree[b] = sc[0] + sc[1] + sc[2] + sc[3];
     }
 }
-
-inline size_t rg_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace

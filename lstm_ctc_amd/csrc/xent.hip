@@ -33,61 +33,14 @@
 //      i, i + 256, ... in sequence, then a xor butterfly over each wave's lanes, then the four waves) and rounds once to float,
 //      like ctc_align.hip's score.
 #include "common.h"
+#include "row_group.h"
 #include <math.h>
 
 #define XE_LOG2E 1.4426950408889634f
 #define XE_LN2 0.6931471805599453f
-#define XE_SCORED 1
-#define XE_CORRECT 2
-#define XE_BAD 4
 #define XE_MAX_GRID 2048                 // blocks of four waves, as stream_grid in misc.hip
 
 namespace {
-
-// ---- reductions over a group of G lanes (G = 16: one DPP row; G = 64: the wave); every lane of the group gets the result
-#define XE_ROW_BUTTERFLY(OP, v, T, TOI, FROMI)                                                                          \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0xB1, 0xf, 0xf, false)));  /* quad_perm [1,0,3,2] */   \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0x4E, 0xf, 0xf, false)));  /* quad_perm [2,3,0,1] */   \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0x141, 0xf, 0xf, false))); /* row_half_mirror */       \
-    v = OP(v, FROMI(__builtin_amdgcn_update_dpp(TOI(v), TOI(v), 0x140, 0xf, 0xf, false)))  /* row_mirror */
-__device__ __forceinline__ int xe_mini(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int xe_id(int a) { return a; }
-
-template <int G> __device__ __forceinline__ float xe_max(float v)
-{
-    if (G == 64) return lc_wave_max(v);
-    XE_ROW_BUTTERFLY(fmaxf, v, float, __float_as_int, __int_as_float);
-    return v;
-}
-template <int G> __device__ __forceinline__ float xe_sum(float v)
-{
-    if (G == 64) return lc_wave_sum(v);
-    XE_ROW_BUTTERFLY(lc_addf, v, float, __float_as_int, __int_as_float);
-    return v;
-}
-template <int G> __device__ __forceinline__ int xe_min(int v)
-{
-    XE_ROW_BUTTERFLY(xe_mini, v, int, xe_id, xe_id);
-    if (G == 64) {
-        const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-        const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-        v = xe_mini(xe_mini(a, b), xe_mini(c, d));
-    }
-    return v;
-}
-
-// What a frame is: its utterance, its time step, whether it is scored.  The waves walk the frames f = t * B + b with a grid
-// stride; (t, b) are carried along by additions (one division pair per wave at the start, none per frame).
-struct XeWalk {
-    int t0, b0, st, sb;
-    __device__ __forceinline__ XeWalk(int first, int stride, int B) : t0(first / B), b0(first % B), st(stride / B), sb(stride % B) {}
-    __device__ __forceinline__ void next(int B)
-    {
-        t0 += st;
-        b0 += sb;
-        if (b0 >= B) { b0 -= B; ++t0; }
-    }
-};
 
 // ------------------------------------------------------------------------------------------ 1a. rows that fit registers
 template <int G, int NE, bool VEC>
@@ -101,7 +54,7 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float *__restrict_
     const int stride = (int)gridDim.x * 4 * FW;      // <= 2048 * 16 frames per pass
     const int first = ((int)blockIdx.x * 4 + ((int)threadIdx.x >> 6)) * FW;
     const long long TB = (long long)T * B;
-    XeWalk w(first, stride, B);
+    RgWalk w(first, stride, B);
     for (long long fb = first; fb < TB; fb += stride, w.next(B)) {
         int b = w.b0 + g, t = w.t0;
 #pragma unroll
@@ -120,7 +73,7 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float *__restrict_
         const size_t row = ((size_t)t * B + b) * (size_t)V;
         if (__builtin_amdgcn_ballot_w64(scored) == 0) {          // nothing to score in this wave: zero rows, no logits read
             if (valid) {
-                if (l == 0) terms[bt] = make_int2(0, bad ? XE_BAD : 0);
+                if (l == 0) terms[bt] = make_int2(0, bad ? RG_BAD : 0);
                 if (grad) {
                     if (VEC) {
 #pragma unroll
@@ -160,7 +113,7 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float *__restrict_
         float m = x[0];
 #pragma unroll
         for (int j = 1; j < NE; ++j) m = fmaxf(m, x[j]);
-        m = xe_max<G>(m);
+        m = rg_max<G>(m);
         // lowest index holding the maximum (idx rises with j inside a lane), and the target's logit in the lane that holds it
         int cand = 0x7fffffff;
         float xt = 0.0f;
@@ -173,18 +126,18 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float *__restrict_
             xt = is_t ? x[j] : xt;
             owner = owner || is_t;
         }
-        const int amax = xe_min<G>(cand);
+        const int amax = rg_min<G>(cand);
         float s = 0.0f;
 #pragma unroll
         for (int j = 0; j < NE; ++j) {
             x[j] = __builtin_amdgcn_exp2f((x[j] - m) * XE_LOG2E);
             s += x[j];
         }
-        s = xe_sum<G>(s);
+        s = rg_sum<G>(s);
         const float lse = m + __builtin_amdgcn_logf(s) * XE_LN2;
         if (scored ? owner : (valid && l == 0))
             terms[bt] = make_int2(scored ? __float_as_int(lse - xt) : 0,
-                                  scored ? (XE_SCORED | (amax == tgt ? XE_CORRECT : 0)) : (bad ? XE_BAD : 0));
+                                  scored ? (RG_SCORED | (amax == tgt ? RG_AGREE : 0)) : (bad ? RG_BAD : 0));
         if (grad && valid) {
             const float inv = scored ? __builtin_amdgcn_rcpf(s) : 0.0f;
             if (VEC) {
@@ -210,24 +163,7 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------ 1b. any row width
-// One pass of a wave over a row of V elements.  VEC (16-byte aligned buffers, any V): the row starts `head` = 0 .. 3 elements
-// short of a 16-byte boundary; lanes 0 .. head - 1 take those as dwords, the body goes in 16-byte accesses, the last
-// (V - head) % 4 elements as dwords again.  A lane's indices rise in the order it visits them.  f1(e): element e; f4(e):
-// elements e .. e + 3, 16-byte aligned.
-template <bool VEC, class F1, class F4>
-__device__ __forceinline__ void xe_walk_row(int lane, int V, int head, F1 f1, F4 f4)
-{
-    if (!VEC) {
-        for (int e = lane; e < V; e += 64) f1(e);
-        return;
-    }
-    if (lane < head) f1(lane);
-    const int nq = (V - head) >> 2;
-    for (int q = lane; q < nq; q += 64) f4(head + 4 * q);
-    const int rest = head + 4 * nq;
-    if (lane < V - rest) f1(rest + lane);
-}
-
+// rg_walk_row (row_group.h) is one pass of a wave over a row.
 template <bool VEC>
 __global__ __launch_bounds__(256) void xent_wide_kernel(const float *__restrict__ logits, int T, int B, int V,
                                                         const int *__restrict__ targets, const int *__restrict__ seq_len,
@@ -237,7 +173,7 @@ __global__ __launch_bounds__(256) void xent_wide_kernel(const float *__restrict_
     const int stride = (int)gridDim.x * 4;
     const int first = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
     const long long TB = (long long)T * B;
-    XeWalk w(first, stride, B);
+    RgWalk w(first, stride, B);
     for (long long fb = first; fb < TB; fb += stride, w.next(B)) {
         const int b = w.b0, t = w.t0;
         const size_t bt = (size_t)b * T + t;
@@ -250,9 +186,9 @@ __global__ __launch_bounds__(256) void xent_wide_kernel(const float *__restrict_
         const float *xr = logits + row;
         float *gr = grad ? grad + row : nullptr;
         if (!scored) {                                                       // wave-uniform
-            if (lane == 0) terms[bt] = make_int2(0, bad ? XE_BAD : 0);
+            if (lane == 0) terms[bt] = make_int2(0, bad ? RG_BAD : 0);
             if (gr)
-                xe_walk_row<VEC>(lane, V, head, [&](int e) { gr[e] = 0.0f; },
+                rg_walk_row<VEC>(lane, V, head, [&](int e) { gr[e] = 0.0f; },
                                  [&](int e) { *(float4 *)(gr + e) = make_float4(0.f, 0.f, 0.f, 0.f); });
             continue;
         }
@@ -262,18 +198,18 @@ __global__ __launch_bounds__(256) void xent_wide_kernel(const float *__restrict_
         auto top = [&](float v, int e) {
             if (v > m || (cand == 0x7fffffff && v == m)) { m = v; cand = e; }
         };
-        xe_walk_row<VEC>(lane, V, head, [&](int e) { top(xr[e], e); },
+        rg_walk_row<VEC>(lane, V, head, [&](int e) { top(xr[e], e); },
                          [&](int e) {
                              const float4 q = *(const float4 *)(xr + e);
                              top(q.x, e); top(q.y, e + 1); top(q.z, e + 2); top(q.w, e + 3);
                          });
         const float lm = m;
         m = lc_wave_max(m);
-        const int amax = xe_min<64>(lm == m ? cand : 0x7fffffff);
+        const int amax = rg_min<64>(lm == m ? cand : 0x7fffffff);
         // pass 2: sum of exponentials, per lane in the order of its visits, then over the lanes
         float s = 0.0f;
         auto ex = [&](float v) { return __builtin_amdgcn_exp2f((v - m) * XE_LOG2E); };
-        xe_walk_row<VEC>(lane, V, head, [&](int e) { s += ex(xr[e]); },
+        rg_walk_row<VEC>(lane, V, head, [&](int e) { s += ex(xr[e]); },
                          [&](int e) {
                              const float4 q = *(const float4 *)(xr + e);
                              s += ex(q.x); s += ex(q.y); s += ex(q.z); s += ex(q.w);
@@ -281,12 +217,12 @@ __global__ __launch_bounds__(256) void xent_wide_kernel(const float *__restrict_
         s = lc_wave_sum(s);
         const float lse = m + __builtin_amdgcn_logf(s) * XE_LN2;
         if (lane == 0)
-            terms[bt] = make_int2(__float_as_int(lse - xr[tgt]), XE_SCORED | (amax == tgt ? XE_CORRECT : 0));
+            terms[bt] = make_int2(__float_as_int(lse - xr[tgt]), RG_SCORED | (amax == tgt ? RG_AGREE : 0));
         // pass 3: the gradient row
         if (gr) {
             const float inv = __builtin_amdgcn_rcpf(s);
             auto g1 = [&](float v, int e) { return ex(v) * inv - (e == tgt ? 1.0f : 0.0f); };
-            xe_walk_row<VEC>(lane, V, head, [&](int e) { gr[e] = g1(xr[e], e); },
+            rg_walk_row<VEC>(lane, V, head, [&](int e) { gr[e] = g1(xr[e], e); },
                              [&](int e) {
                                  const float4 q = *(const float4 *)(xr + e);
                                  *(float4 *)(gr + e) = make_float4(g1(q.x, e), g1(q.y, e + 1), g1(q.z, e + 2), g1(q.w, e + 3));
@@ -296,54 +232,18 @@ __global__ __launch_bounds__(256) void xent_wide_kernel(const float *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------ 2. per-utterance fold
-__device__ __forceinline__ double xe_xor_d(double x, int mask)
-{
-    const int lo = __shfl_xor(__double2loint(x), mask, 64), hi = __shfl_xor(__double2hiint(x), mask, 64);
-    return __hiloint2double(hi, lo);
-}
 __global__ __launch_bounds__(256) void xent_fold_kernel(const int2 *__restrict__ terms, int T, float *__restrict__ loss,
                                                         int *__restrict__ frames, int *__restrict__ correct)
 {
-    __shared__ double sacc[4];
-    __shared__ int sn[4], sc[4], sbad[4];
-    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
-    const int2 *row = terms + (size_t)b * T;
-    double acc = 0.0;
-    int n = 0, c = 0, bad = 0;
-    for (int t = tid; t < T; t += 256) {             // thread i: frames i, i + 256, ... in sequence
-        const int2 w = row[t];
-        if (w.y & XE_SCORED) {
-            acc += (double)__int_as_float(w.x);
-            ++n;
-            c += (w.y & XE_CORRECT) ? 1 : 0;
-        }
-        bad |= w.y & XE_BAD;
-    }
-#pragma unroll
-    for (int mask = 1; mask < 64; mask <<= 1) {      // both lanes of a pair add the same two operands: one result, fixed order
-        acc += xe_xor_d(acc, mask);
-        n += __shfl_xor(n, mask, 64);
-        c += __shfl_xor(c, mask, 64);
-        bad |= __shfl_xor(bad, mask, 64);
-    }
-    if ((tid & 63) == 0) { sacc[wave] = acc; sn[wave] = n; sc[wave] = c; sbad[wave] = bad; }
-    __syncthreads();
-    if (tid == 0) {
-        const double total = (sacc[0] + sacc[1]) + (sacc[2] + sacc[3]);
-        loss[b] = (sbad[0] | sbad[1] | sbad[2] | sbad[3]) ? __int_as_float(0x7fc00000) : (float)total;
-        frames[b] = sn[0] + sn[1] + sn[2] + sn[3];
-        correct[b] = sc[0] + sc[1] + sc[2] + sc[3];
-    }
+    rg_fold(terms, T, loss, frames, correct);
 }
-
-inline size_t xe_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
 extern "C" size_t lc_xent_workspace_bytes(int T, int B, int V)
 {
     if (T <= 0 || B <= 0 || V < 2) return 0;
-    return xe_align256((size_t)T * B * sizeof(int2));            // per frame: its term (float) and a flag word
+    return lc_align256((size_t)T * B * sizeof(int2));            // per frame: its term (float) and a flag word
 }
 
 extern "C" int lc_xent_loss(const float *logits, int T, int B, int V, const int *targets, const int *seq_len, float *loss,

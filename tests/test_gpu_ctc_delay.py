@@ -207,6 +207,43 @@ def test_lambda_zero_reproduces_ctc_loss_and_windowed_ctc():
         check_against_reference(case, 0.0, loss, entry, grad, "lambda 0 " + name, windowed=windowed)      # entry_sum too
 
 
+@pytest.mark.parametrize("L,V", [(5, 8), (40, 8), (40, 129), (100, 8), (200, 8), (400, 8), (1023, 8)])
+def test_lambda_zero_with_windows_is_windowed_ctc_bit_for_bit(L, V):
+    """Both entries run one sweep template, so at lambda 0 (every arc weight is +0.0 or -0.0, and no cell is -0.0) they cannot
+    differ in a bit: one label length per positions-per-lane class, a batch of a feasible utterance, one whose window
+    excludes every frame (+inf, softmax rows) and one with a bad label (NaN, zero rows)."""
+    from lstm_ctc_amd import _lib
+    lib = _lib.load()
+    rng = np.random.RandomState(4000 + 10 * L + V)
+    utts = []
+    for kind in ("fine", "no path", "bad label"):
+        labels = make_labels(rng, V, L)
+        Tb = need_frames(labels) + 3
+        lo, hi = windows_around(rng, random_path(rng, labels, Tb), L)
+        if kind == "no path":
+            lo[L // 2], hi[L // 2] = Tb, -1
+        if kind == "bad label":
+            labels[L // 2] = V - 1
+        utts.append((Tb, labels, lo, hi))
+    case = make_case(rng, V, utts, True)
+    loss, entry, grad = call(case, 0.0, want_entry=False)
+    assert entry is None and np.isfinite(loss[0]) and loss[1] == np.inf and np.isnan(loss[2])
+    T, B = case.T, case.B
+    nbytes = lib.lc_ctc_window_workspace_bytes(T, B, V, case.maxlen)
+    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda")
+    loss_w, grad_w = torch.full((B,), float("nan"), device="cuda"), torch.full((T, B, V), float("nan"), device="cuda")
+    x, flat, offs, seq, lo, hi = (_dev(case.x, np.float32), _dev(case.flat, np.int32), _dev(case.offs, np.int32),
+                                  _dev(case.seq, np.int32), _dev(case.lo, np.int32), _dev(case.hi, np.int32))
+    p = lambda t: t.data_ptr()
+    rc = lib.lc_ctc_loss_windowed(p(x), T, B, V, p(flat), p(offs), p(seq), case.maxlen, p(lo), p(hi), p(loss_w), p(grad_w),
+                                  p(ws), nbytes, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0, lib.lc_last_error()
+    assert np.array_equal(loss.view(np.int32), loss_w.cpu().numpy().view(np.int32)), (loss, loss_w)
+    assert np.array_equal(grad.view(np.int32), grad_w.cpu().numpy().view(np.int32))
+    assert grad[:utts[1][0], 1].any() and not grad[:, 2].any()
+
+
 # ----------------------------------------------------------------------------------------------- identities
 def _long_case(T, V, L, B, windowed):
     rng = np.random.RandomState(T + V)
