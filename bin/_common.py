@@ -260,6 +260,20 @@ def report_consistency(graph):
                % (graph.consistency_weight, graph.cr_loss_total / max(n, 1), n, 100.0 * graph.cr_agree_total / max(n, 1)))
 
 
+def report_chunking(nnet_config):
+    """One INFO line when <nnet-config> sets chunk_frames (the latency-controlled BiLSTM): Nc, Nr, the layers
+    and how far past a chunk's end its logits read, in model frames and in raw frames (x subsample, + right_context).  A
+    config that sets the keys for a model that cannot run them: the FATAL line and exit 1, before a model is built."""
+    from lstm_ctc_amd.nnet.model import chunk_info_line
+    try:
+        line = chunk_info_line(nnet_config)
+    except ValueError as exc:
+        _fatal(str(exc))
+    if line:
+        from lstm_ctc_amd.nnet import tflog
+        tflog.info(line)
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:

@@ -6,7 +6,7 @@ scp order.  An utterance without labels, or whose labels do not fit its frames, 
 import os
 import sys
 
-from _common import build_cli, setup_device
+from _common import build_cli, setup_device, report_chunking
 
 
 def main(args):
@@ -21,6 +21,7 @@ def main(args):
     scores = open(args.scores, "w") if args.scores else None
     nnet_config = nnet.parse_config(args.nnet_config)
     nnet_config['is_training'] = False
+    report_chunking(nnet_config)                          # chunk_frames / lookahead_frames: one INFO line
     filename, tfrecord, _ = nnet.dataset_from_tfrecords(
         tfrecords_scp=args.tfrecords_scp, left_context=nnet_config.get('left_context'),
         right_context=nnet_config.get('right_context'), subsample=nnet_config.get('subsample'), shuffle=False)

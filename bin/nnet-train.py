@@ -6,7 +6,8 @@ import sys
 
 from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
                      report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, delay_keywords,
-                     report_delay_penalty, spec_augment_keywords, report_spec_augment, consistency_keywords, report_consistency)
+                     report_delay_penalty, spec_augment_keywords, report_spec_augment, consistency_keywords, report_consistency,
+                     report_chunking)
 
 
 def main(args):
@@ -22,6 +23,7 @@ def main(args):
         quiet_unless_rank0(rank)
         nnet_config = nnet.parse_config(args.nnet_config)
         nnet_config['is_training'] = True
+        report_chunking(nnet_config)                      # chunk_frames / lookahead_frames: one INFO line
         nnet_type = nnet_config.get('nnet_type')
         filename, tfrecord, input_dim = nnet.dataset_from_tfrecords(
             tfrecords_scp=args.tfrecords_scp, left_context=nnet_config.get('left_context'),

@@ -553,6 +553,37 @@ int lc_length_mask(float *x, int T, int B, int C, int ldx, const int *seq_len, l
 int lc_pack_rows(const float *x, int ldx, const int *rows, int Mp, int C, float *out, int ldo, lc_stream_t stream);
 int lc_unpack_rows(const float *x, int ldx, const int *inverse, int rows, int C, float *out, int ldo, lc_stream_t stream);
 
+/* ------------------------------------------------------------------ chunked batch ---------- */
+/* The layout passes of the latency-controlled BiLSTM (Zhang et al. 2016; Xue & Yan 2017; no reference counterpart; DESIGN.md
+ * 3.13): the backward direction of a layer restarts from a zero state in every chunk of `chunk` frames, after `lookahead`
+ * warm-up frames.  It runs as the ordinary reverse recurrence (lc_lstm_fwd / lc_lstm_bwd, reverse = 1) on a re-laid-out batch:
+ *   nC = ceil(T / chunk) chunks, Tc = min(chunk + lookahead, T) frames each, Bc = nC * B rows;
+ *   the chunked layout is time-major [Tc, Bc, C], chunk row r = c * B + b holds frames [c * chunk, c * chunk + Tc) of
+ *   utterance b, and its length is clamp(seq_len[b] - c * chunk, 0, Tc).
+ *   lc_chunk_gather  (padded -> chunked)  with t = c * chunk + tau:
+ *                    out[(tau * Bc + c * B + b) * ldo + k] = x[(t * B + b) * ldx + k]  if t < T and (!zero_lookahead or
+ *                    tau < chunk), else +0.  zero_lookahead = 0 serves zx; 1 serves dh (the outputs of lookahead frames are
+ *                    discarded, so their upstream gradient is zero).
+ *   lc_chunk_fold    (chunked -> padded)
+ *                    sum_copies = 0: out[t, b, :] = the copy of the frame's own chunk, c = t / chunk, tau = t % chunk, bit
+ *                    for bit (serves hs);
+ *                    sum_copies != 0: out[t, b, :] = the float32 sum over every chunk c with c * chunk <= t < c * chunk + Tc,
+ *                    in ascending c, the first term initialising the sum (no 0 + ...) (serves dz: zx[t] is shared by every
+ *                    chunk copy of frame t);
+ *                    seq_len (device [B] int32) non-NULL: a copy whose tau is at or beyond its chunk row's length is skipped
+ *                    and rows with t >= seq_len[b] are +0 - the result does not depend on what a recurrence left in dead
+ *                    frames.
+ * Every element of out is written on every call (no memset needed).  A pure function of its arguments (no atomics): the same
+ * call gives the same bits.  Elements are indexed in 64 bits.  ldx / ldc / ldo: row pitches in floats (column windows of wider
+ * buffers are fine).  16-byte accesses when C and both pitches are multiples of 4 and both bases 16-byte aligned, a scalar
+ * path otherwise.
+ * LC_EINVAL, with nothing launched and no output touched: T, B, C <= 0; chunk <= 0; lookahead < 0; a NULL x / xc / out; a pitch
+ * below C. */
+int lc_chunk_gather(const float *x, int ldx, int T, int B, int C, int chunk, int lookahead, int zero_lookahead, float *out,
+                    int ldo, lc_stream_t stream);
+int lc_chunk_fold(const float *xc, int ldc, int T, int B, int C, int chunk, int lookahead, int sum_copies,
+                  const int *seq_len /* or NULL */, float *out, int ldo, lc_stream_t stream);
+
 /* ------------------------------------------------------------------ SpecAugment ------------- */
 /* Time and frequency masking of the filterbank input (Park et al., 2019; no reference counterpart), on the spliced and
  * subsampled batch the loader uploads.  x and out are time-major [T * B, D] with row pitches ldx / ldo (floats); out == x (in

@@ -79,6 +79,8 @@ SIGNATURES = {
     "lc_length_mask": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lc_pack_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "lc_unpack_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "lc_chunk_gather": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "lc_chunk_fold": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "lc_spec_augment": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_u32, c_void_p, c_int, c_void_p,
                                 c_void_p]),
     "lc_lstm_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -87,7 +87,8 @@ def _create_logits(nnet_type):
         reg_loss = []
         encoder = None
         if nnet_type == "blstm":
-            encoder = model.encoder()
+            # (latency-controlled mode: one backward final state per chunk - there is no encoder tensor, model.encoder raises)
+            encoder = None if model.chunk else model.encoder()
             w, logq = _label_smoothing_setup(cfg, dev)
             if w > 0:
                 T_, B_, V_ = tbv.shape

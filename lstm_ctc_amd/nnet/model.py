@@ -261,12 +261,69 @@ def config_keep(cfg):
     return float(dr)
 
 
+def chunk_config(cfg):
+    """(Nc, Nr) of the latency-controlled BiLSTM keys ``chunk_frames`` / ``lookahead_frames`` (extension, model frames;
+    DESIGN.md 3.13), validated: (0, 0) when ``chunk_frames`` is absent or 0 - today's model -, else Nc >= 1 and Nr >= 0.
+    The keys change what the model computes, so what cannot run them is refused here, never run without them."""
+    def key(name):
+        v = cfg.get(name)
+        if v is None:
+            return 0
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("%s must be a non-negative integer (model frames), got %r" % (name, v))
+        return int(v)
+    Nc, Nr = key("chunk_frames"), key("lookahead_frames")
+    if Nc == 0:
+        return 0, 0
+    if cfg.get("nnet_type", "blstm") != "blstm":
+        raise ValueError("chunk_frames / lookahead_frames restart the backward direction of nnet_type = blstm; nnet_type = "
+                         "%s has none" % cfg.get("nnet_type"))
+    cd = str(cfg.get("compute_dtype") or "fp32").lower()
+    if cd not in ("fp32", "float32", "f32"):
+        raise ValueError("chunk_frames / lookahead_frames are built for compute_dtype = fp32 only, got compute_dtype = %s" % cd)
+    return Nc, Nr
+
+
+def chunk_horizon(num_layers, Nc, Nr, c=0, T=None):
+    """H_L(c): the logits of chunk c of an L-layer latency-controlled BiLSTM (no splicing) read no input frame at or beyond
+    it.  H_1 = (c + 1) Nc + Nr; a layer above reads its input up to H_l - 1, whose backward outputs come from the chunk that
+    frame lies in: H_{l+1} = ((H_l - 1) // Nc + 1) Nc + Nr.  Clipped to T when given."""
+    clip = (lambda h: h) if T is None else (lambda h: min(h, T))
+    H = clip((c + 1) * Nc + Nr)
+    for _ in range(num_layers - 1):
+        H = clip(((H - 1) // Nc + 1) * Nc + Nr)
+    return H
+
+
+def chunk_horizon_raw(cfg):
+    """(model frames, raw frames) a chunk's logits look past its end at worst, for the INFO line of the command-line tools:
+    H_L(0) - Nc, and that times the subsampling factor plus the splice's right context."""
+    Nc, Nr = chunk_config(cfg)
+    h = chunk_horizon(cfg["num_layers"], Nc, Nr) - Nc
+    return h, h * max(int(cfg.get("subsample") or 0), 1) + int(cfg.get("right_context") or 0)
+
+
+def chunk_info_line(cfg):
+    """The INFO line of nnet-train / -validate / -forward / -align when the mode is on, else None."""
+    Nc, Nr = chunk_config(cfg)
+    if not Nc:
+        return None
+    h, raw = chunk_horizon_raw(cfg)
+    return ("latency-controlled BiLSTM: chunk_frames = %d, lookahead_frames = %d, %d layers: a chunk's logits read %d model "
+            "frames (%d raw frames) past its end" % (Nc, Nr, cfg["num_layers"], h, raw))
+
+
 class Model:
     """Forward / backward of the stack on one batch.  ``x`` is time-major ``[T,B,D]`` on the GPU,
     zero beyond each utterance's length (the pipeline's padding value, nnet/pipeline.py:44)."""
 
     def __init__(self, cfg, device="cuda", seed=None):
         self.cfg = dict(cfg)
+        # Extension keys chunk_frames = Nc, lookahead_frames = Nr (model frames; absent or Nc = 0: off): the latency-controlled
+        # BiLSTM - every layer's backward direction restarts from a zero state in each chunk of Nc frames after Nr lookahead
+        # frames, as the same reverse recurrence on a re-laid-out batch of ceil(T / Nc) * B rows (lc_chunk_gather /
+        # lc_chunk_fold, DESIGN.md 3.13).  Parameters and checkpoints are the plain model's.  fp32 only; refused otherwise.
+        self.chunk, self.lookahead = chunk_config(self.cfg)
         self.device = torch.device(device)
         self.ps = ParamStore(self.cfg, self.device)
         self.ps.init_random(seed)
@@ -338,6 +395,13 @@ class Model:
             self.pack_frames = False
         self.packed = False          # what the last forward() did: True = the input products ran on packed frames
         self._frame_map = None       # (key, the lengths the key was made from, FrameMap) of the last ragged batch
+
+    def lookahead_horizon(self):
+        """Latency-controlled mode: the worst-case number of model frames past a chunk's end that its logits read,
+        H_L(0) - Nc (``chunk_horizon``); None when the mode is off (the whole utterance)."""
+        if not self.chunk:
+            return None
+        return chunk_horizon(self.ps.num_layers, self.chunk, self.lookahead) - self.chunk
 
     def frame_map(self, seq_len, T, B, seq_len_host=None):
         """The FrameMap of this batch, built once per distinct batch.  With ``seq_len_host`` (the lengths as a host array: a
@@ -494,6 +558,10 @@ class Model:
         pk_rows, pk_inverse = fm.device(dev) if self.packed else (None, None)
         inp = x.reshape(rows, D)
         bn_saved = {}
+        chunked = self.chunk > 0
+        if chunked:
+            _, Tc, Bc = ops.chunk_shape(T, B, self.chunk, self.lookahead)
+            len_c = ops.chunk_lengths(seq_len, T, self.chunk, self.lookahead)
 
         def batch_norm(name, t):
             y, mean, var = ops.bn_forward(t, ps.p(name + "/gamma"), ps.p(name + "/beta"), self.is_training,
@@ -520,7 +588,8 @@ class Model:
                 else:
                     zx = self._mm(inp, c["Kx"], bias=c["bias"])                      # hoisted x_t.Kx + b
                 R = ops.gemm(c["proj"], c["Kh"]) if c["proj"] is not None else c["Kh"]
-                cs = torch.empty((rows, N), dtype=torch.float32, device=dev)
+                # (chunked backward direction: its cell state exists in the chunk layout only)
+                cs = None if chunked and d == 1 else torch.empty((rows, N), dtype=torch.float32, device=dev)
                 hs = torch.empty((rows, N), dtype=torch.float32, device=dev)
                 dirs.append(dict(zx=zx, R=R, w_f=c["w_f"], w_i=c["w_i"], w_o=c["w_o"], cs=cs, hs=hs,
                                  reverse=(d == 1)))
@@ -531,8 +600,20 @@ class Model:
             # (split-operand mode, widths up to 320: the fp32 forward recurrence is the faster one since its operands are
             # requested a step ahead - 1.77 against 2.11 us per step at N = 320, 1.44 / 1.72 at 256; from 512 up the
             # split-operand kernel leads, 2.56 against 2.86: profiles/r5_persist_probe_ahead.txt)
-            ops.lstm_fwd(dirs, seq_len, T, B, N, self.forget_bias, bf16=self.bf16,
-                         x3=self.x3_rec_fwd and x3_forward_recurrence(N))
+            if chunked:
+                # latency-controlled: the forward direction as it is; the backward direction on the chunked batch - Bc rows
+                # of Tc frames, each with its own length, from a zero state - and its kept frames folded back
+                fd, bd = dirs
+                ops.lstm_fwd([fd], seq_len, T, B, N, self.forget_bias)
+                ck = dict(zx=ops.chunk_gather(bd["zx"], T, B, self.chunk, self.lookahead), R=bd["R"], w_f=bd["w_f"],
+                          w_i=bd["w_i"], w_o=bd["w_o"], cs=torch.empty((Tc * Bc, N), dtype=torch.float32, device=dev),
+                          hs=torch.empty((Tc * Bc, N), dtype=torch.float32, device=dev), reverse=True)
+                ops.lstm_fwd([ck], len_c, Tc, Bc, N, self.forget_bias)
+                ops.chunk_fold(ck["hs"], T, B, self.chunk, self.lookahead, out=bd["hs"])
+                bd["chunked"], bd["zx"] = ck, None          # the padded zx is spent: the gates live in the chunk layout
+            else:
+                ops.lstm_fwd(dirs, seq_len, T, B, N, self.forget_bias, bf16=self.bf16,
+                             x3=self.x3_rec_fwd and x3_forward_recurrence(N))
             for dd in dirs:
                 if dd.get("hs_bf16") is not None:
                     self._adopt_shadow(dd["hs"], dd["hs_bf16"])
@@ -593,12 +674,16 @@ class Model:
         else:
             logits = self._mm(inp, ps.p("Variable"), bias=ps.p("Variable_1"))
         self.saved = dict(layers=layers, head=head, T=T, B=B, seq_len=seq_len, drop_seed=drop_seed, bn=bn_saved,
-                          top=inp, frames=(pk_rows, pk_inverse) if self.packed else None)
+                          top=inp, frames=(pk_rows, pk_inverse) if self.packed else None,
+                          chunks=(Tc, Bc, len_c) if chunked else None)
         return logits.view(T, B, ps.V)
 
     def encoder(self):
         """Final (c, m) states of the last layer, concatenated as bilstm.py:206-208.  Computed lazily
         from the saved activations (graph.py never uses it)."""
+        if self.chunk:
+            raise NotImplementedError("encoder(): with chunk_frames / lookahead_frames set the backward direction has one "
+                                      "final state per chunk, not one per utterance")
         sv = self.saved
         B = sv["B"]
         last = sv["layers"][-1]
@@ -718,6 +803,14 @@ class Model:
                 if ps.peep:
                     o = ps.offsets[c["prefix"] + "/w_f_diag"]
                     dpeep = ps.grad[o:o + 3 * N]
+                ck = dirs[d].get("chunked")
+                if ck is not None:
+                    # latency-controlled backward direction: its BPTT runs on the chunk rows; the outputs of lookahead
+                    # frames were discarded, so their upstream gradient is zero (the state still carries gradient through them)
+                    bdirs.append(dict(gates=ck["zx"], RT=RT, w_f=c["w_f"], w_i=c["w_i"], w_o=c["w_o"], cs=ck["cs"],
+                                      dh=ops.chunk_gather(dh, T, B, self.chunk, self.lookahead, zero_lookahead=True),
+                                      dpeep=dpeep, dbias=ps.g(c["prefix"] + "/bias"), reverse=True))
+                    continue
                 bdirs.append(dict(gates=dirs[d]["zx"], RT=RT, w_f=c["w_f"], w_i=c["w_i"], w_o=c["w_o"],
                                   cs=dirs[d]["cs"], dh=dh, dpeep=dpeep, dbias=ps.g(c["prefix"] + "/bias"),
                                   reverse=dirs[d]["reverse"]))
@@ -735,7 +828,19 @@ class Model:
                     bdirs[-1]["dz_x3"] = torch.empty((rows, 12 * N), dtype=torch.bfloat16, device=dY.device)
             if buckets is not None:
                 buckets.wait()                   # a persistent recurrence needs every CU: no collective kernel beside it
-            ops.lstm_bwd(bdirs, sv["seq_len"], T, B, N, bf16=self.bf16, x3=self.x3_rec_bwd)
+            if sv["chunks"] is not None:
+                # each direction in its own layout; dbias / dpeep of the chunked one accumulate over all chunk rows, which is
+                # the right sum.  zx[t] was shared by every chunk copy of frame t: its gradient is the sum over the copies
+                # (fixed order), and that padded dz takes the place of the recurrence's for dKx, dX and the packed path.
+                # dz_c stays for dR, the one product in the chunk layout.
+                Tc, Bc, len_c = sv["chunks"]
+                ops.lstm_bwd(bdirs[:1], sv["seq_len"], T, B, N)
+                ops.lstm_bwd(bdirs[1:], len_c, Tc, Bc, N)
+                bdirs[1]["gates_c"] = bdirs[1]["gates"]
+                bdirs[1]["gates"] = ops.chunk_fold(bdirs[1]["gates_c"], T, B, self.chunk, self.lookahead, sum_copies=True,
+                                                   seq_len=sv["seq_len"])
+            else:
+                ops.lstm_bwd(bdirs, sv["seq_len"], T, B, N, bf16=self.bf16, x3=self.x3_rec_bwd)
             if buckets is not None and i + 1 < ps.num_layers and not self.overlap_wgrad:
                 buckets.issue(*self.layer_grad_range(i + 1))      # runs beside this layer's weight-gradient GEMMs
             for bd in bdirs:
@@ -780,7 +885,8 @@ class Model:
                 ev = torch.cuda.Event()
                 ev.record(main)
                 self._side.wait_event(ev)
-                keepalive.append((dY, bdirs, dzp))    # read on the side stream after main has dropped its references
+                # read on the side stream after main has dropped its references (dirs / bdirs: the chunked hs and dz too)
+                keepalive.append((dY, bdirs, dzp, dirs))
             with torch.cuda.stream(self._side if overlap else main):
                 for d, c in enumerate(cells):
                     pre = c["prefix"]
@@ -788,8 +894,15 @@ class Model:
                     gk = ps.g(pre + "/kernel")
                     I = c["I"]
                     self._mm(xin, dzs_in[d], ta=True, out=gk[:I], x3_ok=side_x3)             # dKx = X^T dZ
-                    if T > 1:                                                                # dR = M'_{prev}^T dZ
-                        if dirs[d]["reverse"]:
+                    steps = T
+                    dz_c = bdirs[d].get("gates_c")
+                    if dz_c is not None:         # chunked direction: the recurrence's own rows, one chunk step apart
+                        steps = sv["chunks"][0]
+                    if steps > 1:                                                            # dR = M'_{prev}^T dZ
+                        if dz_c is not None:
+                            Bc = sv["chunks"][1]
+                            hprev, dzs = dirs[d]["chunked"]["hs"][Bc:], dz_c[:steps * Bc - Bc]
+                        elif dirs[d]["reverse"]:
                             hprev, dzs = hs[B:], dz[:rows - B]
                         else:
                             hprev, dzs = hs[:rows - B], dz[B:]
@@ -828,7 +941,7 @@ class Model:
                     if c["proj"] is not None:
                         gp = ps.g(pre + "/projection/kernel")
                         self._mm(hs, half, ta=True, out=gp, x3_ok=side_x3)                   # from m_t = m'_t.proj
-                        if T > 1:
+                        if steps > 1:
                             ops.gemm(dR, c["Kh"], tb=True, out=gp, beta=1.0)                 # from R = proj.Kh
                     if need_dinp and not overlap and not fuse_dx and not fuse_dx32:
                         self._mm(dzs_in[d], c["Kx"], tb=True, out=dxo, beta=(0.0 if d == 0 else 1.0),

@@ -782,6 +782,69 @@ def unpack_rows(x, inverse, out=None):
     return _gather_rows("lc_unpack_rows", x, inverse, out)
 
 
+# ------------------------------------------------------------------------------------------ chunked batch (LC-BLSTM)
+def chunk_shape(T, B, chunk, lookahead):
+    """(nC, Tc, Bc) of the chunked layout of a [T, B] batch: nC = ceil(T / chunk) chunks of Tc = min(chunk + lookahead, T)
+    frames, Bc = nC * B rows (chunk row c * B + b)."""
+    T, B, chunk, lookahead = int(T), int(B), int(chunk), int(lookahead)
+    if T <= 0 or B <= 0 or chunk <= 0 or lookahead < 0:
+        raise ValueError("chunk_shape: need T, B, chunk >= 1 and lookahead >= 0, got %r" % ((T, B, chunk, lookahead),))
+    nC = -(-T // chunk)
+    return nC, min(chunk + lookahead, T), nC * B
+
+
+def chunk_lengths(seq_len, T, chunk, lookahead):
+    """Lengths of the chunk rows, [nC * B] int32 on seq_len's device: row c * B + b has clamp(seq_len[b] - c * chunk, 0, Tc)
+    frames.  Plain torch, no kernel of ours and no synchronisation."""
+    nC, Tc, _ = chunk_shape(T, seq_len.numel(), chunk, lookahead)
+    start = torch.arange(nC, dtype=torch.int32, device=seq_len.device) * int(chunk)
+    return (seq_len.to(torch.int32).reshape(1, -1) - start.reshape(-1, 1)).clamp_(0, Tc).reshape(-1).contiguous()
+
+
+def _rows_pitch(t, C):
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), C)
+
+
+def chunk_gather(x, T, B, chunk, lookahead, zero_lookahead=False, out=None):
+    """Padded -> chunked (lc_chunk_gather): x [T*B, C] time-major f32 (a 2-D view, last stride 1) -> out [Tc*Bc, C],
+    out[tau * Bc + c * B + b] = x[(c * chunk + tau) * B + b] where that frame exists (and, with zero_lookahead, tau < chunk),
+    +0 elsewhere.  Every element of out is written."""
+    lib = _lib.load()
+    _require_cuda(x, out)
+    _, Tc, Bc = chunk_shape(T, B, chunk, lookahead)
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1 and x.shape[0] == T * B, (x.shape, x.stride())
+    C = x.shape[1]
+    if out is None:
+        out = torch.empty((Tc * Bc, C), dtype=torch.float32, device=x.device)
+    assert out.dim() == 2 and tuple(out.shape) == (Tc * Bc, C) and out.dtype == torch.float32 and out.stride(1) == 1
+    ev = _prof_begin()
+    _lib.check(lib.lc_chunk_gather(_ptr(x), _rows_pitch(x, C), T, B, C, int(chunk), int(lookahead), int(bool(zero_lookahead)),
+                                   _ptr(out), _rows_pitch(out, C), _stream()), "lc_chunk_gather")
+    _prof_end("chunk", 8.0 * Tc * Bc * C, ev)
+    return out
+
+
+def chunk_fold(xc, T, B, chunk, lookahead, sum_copies=False, seq_len=None, out=None):
+    """Chunked -> padded (lc_chunk_fold): xc [Tc*Bc, C] -> out [T*B, C].  sum_copies=False: each frame's copy from its own
+    chunk, bit for bit; True: the fp32 sum of every chunk copy of the frame, in ascending chunk order.  seq_len ([B] int32,
+    optional): dead copies are skipped and rows beyond each length are +0."""
+    lib = _lib.load()
+    _require_cuda(xc, seq_len, out)
+    _, Tc, Bc = chunk_shape(T, B, chunk, lookahead)
+    assert xc.dim() == 2 and xc.dtype == torch.float32 and xc.stride(1) == 1 and xc.shape[0] == Tc * Bc, (xc.shape, xc.stride())
+    C = xc.shape[1]
+    if seq_len is not None:
+        assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+    if out is None:
+        out = torch.empty((T * B, C), dtype=torch.float32, device=xc.device)
+    assert out.dim() == 2 and tuple(out.shape) == (T * B, C) and out.dtype == torch.float32 and out.stride(1) == 1
+    ev = _prof_begin()
+    _lib.check(lib.lc_chunk_fold(_ptr(xc), _rows_pitch(xc, C), T, B, C, int(chunk), int(lookahead), int(bool(sum_copies)),
+                                 _ptr(seq_len), _ptr(out), _rows_pitch(out, C), _stream()), "lc_chunk_fold")
+    _prof_end("chunk", 4.0 * C * (T * B + (Tc * Bc if sum_copies else T * B)), ev)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ SpecAugment
 def _tbd_pitch(t, T, B, D):
     """Row pitch of a time-major [T, B, D] tensor whose T * B rows lie at one pitch (a column window of a wider buffer is
