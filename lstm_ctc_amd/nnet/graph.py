@@ -12,6 +12,8 @@ so ``nnet.train`` / ``nnet.validate`` (funcs.py) read exactly like the reference
   gradient buffer is summed with ONE RCCL all-reduce before the clip, so N ranks x B utterances
   reproduce a single batch of N*B (the clip at graph.py:190 acts on the total gradient of a SUM loss).
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -125,21 +127,68 @@ class _FallbackLatch:
     workgroups from being co-resident - must not be paid on every step: after LATCH_AFTER consecutive failures the
     graph stays on the launch train for the rest of the run.  Every failure is logged."""
     LATCH_AFTER = 2
+    AS_WELL = "LSTM recurrence failed on the launch train as well (status {status})"
 
     def __init__(self):
-        self.consecutive, self.latched = 0, False
+        self.consecutive, self.latched, self.total = 0, False, 0
 
-    def good(self):
-        self.consecutive = 0
+    def run(self, fn, before_retry=None, error=AS_WELL, latched_error=None):
+        """``fn() -> (result, status)``, status the LSTM status word behind it: the result of the first try when it is 0 -
+        else, after ``before_retry()`` (the caller puts back what the failed try advanced), of a second one under
+        ``ops.force_launch_train()``.  Latched, the only try is the forced one.  RuntimeError(``error``, or
+        ``latched_error`` for a latched graph; ``{status}`` is filled in) when the launch train fails too."""
+        latched = self.latched
+        if not latched:
+            result, status = fn()
+            if status == 0:
+                self.consecutive = 0
+                return result
+            self.failed(status)
+            if before_retry is not None:
+                before_retry()
+        with ops.force_launch_train():
+            result, status = fn()
+        if status != 0:
+            raise RuntimeError((latched_error if latched and latched_error else error).format(status=status))
+        return result
 
-    def failed(self, status, total):
+    def failed(self, status):
         from . import tflog
+        self.total += 1
         self.consecutive += 1
         self.latched = self.consecutive >= self.LATCH_AFTER
         tflog.info("persistent LSTM launch did not complete (status %d, fallback #%d); re-running the step with the "
-                   "per-step launch train%s" % (status, total, (" - and staying on it for the rest of this run (%d "
-                                                                "failures in a row)" % self.consecutive)
+                   "per-step launch train%s" % (status, self.total, (" - and staying on it for the rest of this run (%d "
+                                                                     "failures in a row)" % self.consecutive)
                                                 if self.latched else ""))
+
+
+class _HostScalars:
+    """The device scalars a step wants on the host, by name.  ``add`` collects one-element tensors of any dtype (float32 and
+    int32 widen to float64 exactly), ``fetch`` moves all of them in ONE device-to-host copy - the step's single sync - and
+    returns {name: Python float}."""
+
+    def __init__(self):
+        self.names, self.parts = [], []
+
+    def add(self, name, t):
+        if name in self.names:
+            raise KeyError("host scalar %r collected twice" % name)
+        self.names.append(name)
+        self.parts.append(t.to(torch.float64).reshape(1))
+
+    def fetch(self):
+        return dict(zip(self.names, torch.cat(self.parts).cpu().tolist()))
+
+
+def _checked_number(name, value, lower, strict, must_be, integer=False):
+    """``value`` as a float (``integer``: an int) when it is a finite number - never a bool - that is > ``lower`` (``strict``)
+    or >= it; else ValueError("<name> must be <must_be>, got <value>")."""
+    kinds = (int, np.integer) if integer else (int, float, np.integer, np.floating)
+    if (isinstance(value, bool) or not isinstance(value, kinds) or not (integer or np.isfinite(value))
+            or (not value > lower if strict else value < lower)):
+        raise ValueError("%s must be %s, got %r" % (name, must_be, value))
+    return int(value) if integer else float(value)
 
 
 class CTCGraph:
@@ -214,32 +263,22 @@ class CTCGraph:
         if teacher_weight is not None:
             if objective == "kd":
                 raise ValueError("objective=\"kd\" is the distillation term alone (weight 1): it takes no teacher_weight")
-            if (isinstance(teacher_weight, bool) or not isinstance(teacher_weight, (int, float, np.integer, np.floating))
-                    or not np.isfinite(teacher_weight) or not teacher_weight > 0):
-                raise ValueError("teacher_weight must be a finite float > 0 or None, got %r" % (teacher_weight,))
-            teacher_weight = float(teacher_weight)
-        if (isinstance(teacher_temperature, bool) or not isinstance(teacher_temperature, (int, float, np.integer, np.floating))
-                or not np.isfinite(teacher_temperature) or not teacher_temperature > 0):
-            raise ValueError("teacher_temperature must be finite and > 0, got %r" % (teacher_temperature,))
+            teacher_weight = _checked_number("teacher_weight", teacher_weight, 0, True, "a finite float > 0 or None")
         self.teacher_weight = teacher_weight
-        self.teacher_temperature = float(teacher_temperature)
+        self.teacher_temperature = _checked_number("teacher_temperature", teacher_temperature, 0, True, "finite and > 0")
         self.needs_teacher = objective == "kd" or teacher_weight is not None
         self.kd_frames_total = self.kd_agree_total = 0
         if align_window is not None:
             if objective != "ctc":
                 raise ValueError("align_window constrains the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
-            if isinstance(align_window, bool) or not isinstance(align_window, (int, np.integer)) or align_window < 0:
-                raise ValueError("align_window must be an int >= 0 (frames) or None, got %r" % (align_window,))
-            align_window = int(align_window)
+            align_window = _checked_number("align_window", align_window, 0, False, "an int >= 0 (frames) or None",
+                                           integer=True)
         self.align_window = align_window
         self.windows_constrained = self.windows_unconstrained = 0
         if delay_penalty is not None:
             if objective != "ctc":
                 raise ValueError("delay_penalty tilts the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
-            if (isinstance(delay_penalty, bool) or not isinstance(delay_penalty, (int, float, np.integer, np.floating))
-                    or not np.isfinite(delay_penalty) or delay_penalty < 0):
-                raise ValueError("delay_penalty must be a finite float >= 0 or None, got %r" % (delay_penalty,))
-            delay_penalty = float(delay_penalty)
+            delay_penalty = _checked_number("delay_penalty", delay_penalty, 0, False, "a finite float >= 0 or None")
         self.delay_penalty = delay_penalty
         self.entry_sum_total, self.entry_labels_total = 0.0, 0
         self.spec_layout = None
@@ -255,16 +294,13 @@ class CTCGraph:
             if objective != "ctc":
                 raise ValueError("consistency_weight pairs two views under the CTC criterion: it needs objective=\"ctc\", "
                                  "not \"%s\"" % objective)
-            if (isinstance(consistency_weight, bool)
-                    or not isinstance(consistency_weight, (int, float, np.integer, np.floating))
-                    or not np.isfinite(consistency_weight) or not consistency_weight > 0):
-                raise ValueError("consistency_weight must be a finite float > 0 or None, got %r" % (consistency_weight,))
+            consistency_weight = _checked_number("consistency_weight", consistency_weight, 0, True,
+                                                 "a finite float > 0 or None")
             if teacher_weight is not None:
                 raise ValueError("consistency_weight does not combine with teacher_weight (a doubled teacher tensor is not built)")
             if spec_augment is None and config_keep(nnet_config) >= 1.0:
                 raise ValueError("consistency_weight needs two views that differ: spec_augment or dropout (the model has "
                                  "neither, the term would be 0)")
-            consistency_weight = float(consistency_weight)
         self.consistency_weight = consistency_weight
         self.cr_loss_total, self.cr_frames_total, self.cr_agree_total = 0.0, 0, 0
         self.specaug_frames_masked = self.specaug_frames = self.specaug_bins_masked = self.specaug_bins = 0
@@ -292,7 +328,6 @@ class CTCGraph:
         self.drop_seed = 0 if seed is None else int(seed)
         if self.world > 1:
             self.drop_seed = (self.drop_seed * 0x9E3779B1 + (self.rank + 1) * 0x85EBCA6B) & 0x7FFFFFFF
-        self.persist_fallbacks = 0     # steps re-run on the launch train after a persistent launch failed
         self._fallback = _FallbackLatch()
         # per-layer gradient buckets, all-reduced beside the lower layers' weight-gradient GEMMs (dp.GradientBuckets);
         # LC_DP_BUCKETS=0: one all-reduce of the whole flat gradient after the backward
@@ -317,6 +352,11 @@ class CTCGraph:
         if key not in self.keys:
             raise KeyError(key)
         return key
+
+    @property
+    def persist_fallbacks(self):
+        """Steps re-run on the launch train after a persistent launch failed."""
+        return self._fallback.total
 
     # -------------------------------------------------------------------------------------------------
     def _upload(self, batch):
@@ -396,6 +436,24 @@ class CTCGraph:
                              "blank = %d)" % (V - 1, int(flat.min()), int(flat.max()), V, V - 1),
                              "another rank's nnet_target holds a label outside [0, %d)" % (V - 1))
 
+    def _upload_all(self, batch):
+        """What ``step`` consumes of ``batch``, by name: the eight values of ``_upload`` plus ``frame_target`` (device, host;
+        objective = xent), ``windows`` (lo, hi on the device, constrained on the host; align_window) and ``teacher`` (scores,
+        length on the device) - each None when the graph does not use it or the batch carries none (``step`` raises for
+        that).  Copies and ``ops.label_windows``: nothing here raises for the batch's CONTENT."""
+        x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = self._upload(batch)
+        up = SimpleNamespace(x=x, seq_d=seq_d, seq=seq, flat_d=flat_d, offs_d=offs_d, flat=flat, offs=offs, maxlen=maxlen,
+                             frame_target=None, windows=None, teacher=None)
+        if self.objective == "xent":
+            up.frame_target = self._upload_frame_target(batch)
+        elif self.align_window is not None:
+            windows = self._upload_windows(batch, flat, offs, seq)
+            up.windows = None if windows[0] is None else windows
+        if self.needs_teacher:
+            teacher = self._upload_teacher(batch)
+            up.teacher = None if teacher[0] is None else teacher
+        return up
+
     def stage(self, batch):
         """Uploads ``batch`` on a side stream NOW, to be consumed by a later ``step(None, staged=...)``: called for batch
         k + 1 before step k is enqueued, the copy runs under step k's kernels instead of in front of step k + 1's.  Pure
@@ -404,13 +462,7 @@ class CTCGraph:
         if getattr(self, "_h2d_stream", None) is None:
             self._h2d_stream = torch.cuda.Stream(dev)
         with torch.cuda.stream(self._h2d_stream):
-            up = self._upload(batch)
-            if self.objective == "xent":
-                up = up + self._upload_frame_target(batch)
-            elif self.align_window is not None:
-                up = up + self._upload_windows(batch, up[5], up[6], up[2])
-            if self.needs_teacher:
-                up = up + self._upload_teacher(batch)
+            up = self._upload_all(batch)
             ev = torch.cuda.Event()
             ev.record()
         return up, ev
@@ -423,44 +475,33 @@ class CTCGraph:
             up, ev = staged
             cur = torch.cuda.current_stream(self.model.device)
             cur.wait_event(ev)
-            for t in up:
-                if torch.is_tensor(t):
-                    t.record_stream(cur)          # allocated on the copy stream, consumed on this one
+            for field in vars(up).values():
+                for t in field if isinstance(field, tuple) else (field,):
+                    if torch.is_tensor(t):
+                        t.record_stream(cur)      # allocated on the copy stream, consumed on this one
         else:
-            up = self._upload(batch)
-            if self.objective == "xent":
-                up = up + self._upload_frame_target(batch)
-            elif self.align_window is not None:
-                up = up + self._upload_windows(batch, up[5], up[6], up[2])
-            if self.needs_teacher:
-                up = up + self._upload_teacher(batch)
-        teacher = None
-        if self.needs_teacher:
-            up, teacher = up[:-2], up[-2:]
-            if teacher[0] is None:
-                raise ValueError("teacher_weight / objective = kd needs teacher_scores and teacher_length in the batch "
-                                 "(create_pipeline_sequence_batch(..., teacher_scores=...))")
-        x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = up[:8]
-        ft_d = windows = None
+            up = self._upload_all(batch)
+        if self.needs_teacher and up.teacher is None:
+            raise ValueError("teacher_weight / objective = kd needs teacher_scores and teacher_length in the batch "
+                             "(create_pipeline_sequence_batch(..., teacher_scores=...))")
+        frame_target = windows = None
         if self.objective == "xent":                  # reads no nnet_target: has_label = 0 corpora are fine
-            ft_d, ft = up[8:]
-            self._validate_frame_targets(ft, seq)
-        elif self.objective == "kd":                  # neither
-            pass
-        else:
-            self._validate_labels(flat)
+            frame_target, ft_host = up.frame_target
+            self._validate_frame_targets(ft_host, up.seq)
+        elif self.objective == "ctc":                 # (kd reads neither)
+            self._validate_labels(up.flat)
             if self.align_window is not None:
-                lo_d, hi_d, constrained = up[8:]
-                if lo_d is None:
+                if up.windows is None:
                     raise ValueError("align_window needs frame_target in the batch "
                                      "(create_pipeline_sequence_batch(..., frame_targets=...))")
+                lo_d, hi_d, constrained = up.windows
                 windows = (lo_d, hi_d)
                 self.windows_constrained += int(constrained.sum())
                 self.windows_unconstrained += int(len(constrained) - constrained.sum())
-        out = self.step_device(x, seq_d, flat_d, offs_d, maxlen, int(len(flat)), fetch_eval=fetch_eval,
-                               fetch_logits=fetch_logits, train=train, flat_host=flat, offs_host=offs, seq_host=seq,
-                               frame_target=ft_d, windows=windows, teacher=teacher)
-        out["sequence_length"] = np.concatenate([seq, seq]) if "cr_loss" in out else seq      # what the device processed
+        out = self.step_device(up.x, up.seq_d, up.flat_d, up.offs_d, up.maxlen, int(len(up.flat)), fetch_eval=fetch_eval,
+                               fetch_logits=fetch_logits, train=train, flat_host=up.flat, offs_host=up.offs, seq_host=up.seq,
+                               frame_target=frame_target, windows=windows, teacher=up.teacher)
+        out["sequence_length"] = np.concatenate([up.seq, up.seq]) if "cr_loss" in out else up.seq   # what the device processed
         return out
 
     def step_device(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval=False, fetch_logits=False, train=None,
@@ -476,63 +517,52 @@ class CTCGraph:
         NaN outputs and makes the optimizer skip its update on the device; the word is read at the step's one sync
         point and the step is then re-run, in this process, with the per-step launch train."""
         train = self.training if train is None else train
-        counters = (self.global_step, self.drop_seed, self.opt_step)
         if self.align_window is not None and windows is None:
             raise ValueError("align_window needs the label windows (step: frame_target in the batch, frame_targets= of the "
                              "pipeline; step_device: windows=)")
         if self.needs_teacher and (teacher is None or teacher[0] is None):
             raise ValueError("teacher_weight / objective = kd needs the teacher scores (step: teacher_scores in the batch, "
                              "teacher_scores= of the pipeline; step_device: teacher=)")
-        args = (x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host, seq_host,
-                frame_target, windows, teacher)
-        if self._fallback.latched:                     # co-residency is structurally unavailable: stay on the train
-            with ops.force_launch_train():
-                out, status = self._step_once(*args)
-            if status != 0:
-                raise RuntimeError("LSTM recurrence failed on the launch train (status %d)" % status)
-            return out
-        out, status = self._step_once(*args)
-        if status == 0:
-            self._fallback.good()
-            return out
-        self.global_step, self.drop_seed, self.opt_step = counters
-        self.persist_fallbacks += 1
-        self._fallback.failed(status, self.persist_fallbacks)
-        with ops.force_launch_train():
-            out, status = self._step_once(*args)
-        if status != 0:
-            raise RuntimeError("LSTM recurrence failed on the launch train as well (status %d)" % status)
-        return out
+        b = SimpleNamespace(x=x, seq_d=seq_d, flat_d=flat_d, offs_d=offs_d, maxlen=maxlen, size=size, flat=flat_host,
+                            offs=offs_host, seq=seq_host, frame_target=frame_target, windows=windows, teacher=teacher,
+                            pairs=None)
+        counters = (self.global_step, self.drop_seed, self.opt_step)
 
-    def _step_once(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
-                   seq_host=None, frame_target=None, windows=None, teacher=None):
-        dev = self.model.device
-        ops.lstm_status(dev).zero_()
+        def restore():
+            self.global_step, self.drop_seed, self.opt_step = counters
+
+        return self._fallback.run(lambda: self._step_once(b, fetch_eval=fetch_eval, fetch_logits=fetch_logits, train=train),
+                                  before_retry=restore,       # (latched: co-residency is structurally unavailable)
+                                  latched_error="LSTM recurrence failed on the launch train (status {status})")
+
+    def _step_once(self, b, fetch_eval, fetch_logits, train):
+        """One try of the step on ``b``, the arguments of ``step_device`` by name (``flat`` / ``offs`` / ``seq``: the host's
+        copies or None): (outputs, 0), or (None, status) when a recurrence failed.  ``b`` is not changed - the retry reads it
+        again."""
+        ops.lstm_status(self.model.device).zero_()
         self.global_step += 1
         self.drop_seed = (self.drop_seed * 1664525 + 1013904223) & 0x7FFFFFFF
-        pairs = None
         if train and self.consistency_weight is not None:    # every utterance twice; out of place: the caller keeps its x
-            pairs = seq_d
-            x = torch.cat([x, x], dim=1)
-            lo_d, hi_d = windows if windows is not None else (None, None)
-            seq_d, flat_d, offs_d, lo_d, hi_d = double_batch(seq_d, flat_d, offs_d, lo_d, hi_d)
-            windows = (lo_d, hi_d) if windows is not None else None
-            if seq_host is not None:
-                seq_host = np.concatenate([seq_host, seq_host])
-            if offs_host is not None:
-                _, flat_host, offs_host, _, _ = double_batch(None, flat_host, np.asarray(offs_host))
-            size = 2 * size
-        specaug_counts = None
+            x = torch.cat([b.x, b.x], dim=1)
+            lo_d, hi_d = b.windows if b.windows is not None else (None, None)
+            seq_d, flat_d, offs_d, lo_d, hi_d = double_batch(b.seq_d, b.flat_d, b.offs_d, lo_d, hi_d)
+            flat, offs = b.flat, b.offs
+            if offs is not None:
+                _, flat, offs, _, _ = double_batch(None, flat, np.asarray(offs))
+            b = SimpleNamespace(**dict(vars(b), x=x, seq_d=seq_d, flat_d=flat_d, offs_d=offs_d, flat=flat, offs=offs,
+                                       seq=None if b.seq is None else np.concatenate([b.seq, b.seq]), size=2 * b.size,
+                                       windows=None if b.windows is None else (lo_d, hi_d),
+                                       pairs=b.seq_d))           # pairs: the [B] lengths; everything else is the 2B batch
+        x, specaug_counts = b.x, None
         if train and self.spec_augment is not None:          # out of place: the caller keeps its x
-            x = ops.spec_augment(x, seq_d, self.spec_augment, self.spec_layout, self.drop_seed)
-            if seq_host is not None:
+            x = ops.spec_augment(x, b.seq_d, self.spec_augment, self.spec_layout, self.drop_seed)
+            if b.seq is not None:
                 from . import augment
                 sub = self.spec_layout.subsample
-                specaug_counts = augment.masked_shares(augment.mask_plan(self.drop_seed, seq_host, self.spec_augment, sub),
-                                                       seq_host, self.spec_augment, sub)
-        logits = self.model.forward(x, seq_d, drop_seed=self.drop_seed, seq_len_host=seq_host)      # [T,B,V]
-        out, status = self._finish_step(logits, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host,
-                                        offs_host, frame_target, windows, teacher, pairs)
+                specaug_counts = augment.masked_shares(augment.mask_plan(self.drop_seed, b.seq, self.spec_augment, sub),
+                                                       b.seq, self.spec_augment, sub)
+        logits = self.model.forward(x, b.seq_d, drop_seed=self.drop_seed, seq_len_host=b.seq)      # [T,B,V]
+        out, status = self._finish_step(logits, b, fetch_eval=fetch_eval, fetch_logits=fetch_logits, train=train)
         if status == 0 and train and self.spec_augment is not None:          # a failed step is re-run: count it once
             self.specaug_steps += 1
             if specaug_counts is not None:
@@ -542,96 +572,68 @@ class CTCGraph:
                 self.specaug_bins += specaug_counts[3]
         return out, status
 
-    def _finish_step(self, logits, seq_d, flat_d, offs_d, maxlen, size, fetch_eval, fetch_logits, train, flat_host, offs_host,
-                     frame_target, windows, teacher, pairs=None):
-        """What follows the forward in ``_step_once``: criterion, backward, optimizer, the step's one sync.  ``pairs``: the [B]
-        lengths of a batch that ``_step_once`` doubled for consistency_weight (everything else is then the 2B batch)."""
-        dev = self.model.device
-        if self.objective == "xent":
-            return self._finish_xent(logits, seq_d, frame_target, fetch_eval, fetch_logits, train, teacher)
-        if self.objective == "kd":
-            return self._finish_kd(logits, seq_d, teacher, fetch_eval, fetch_logits, train)
+    KD_KEYS = ("kd_loss", "kd_frames", "kd_agree")           # the teacher term's outputs (objective = kd: the criterion's)
+    CR_KEYS = ("cr_loss", "cr_frames", "cr_agree")           # the consistency term's
+
+    # A criterion calls its ``ops.*`` loss on the logits and returns (grad, scalars, outputs): the gradient buffer that the
+    # shared terms accumulate into (None when not training); ``scalars()`` -> the (name, device scalar) pairs it wants on the
+    # host, reduced at the step's one copy; ``outputs(host, out, fetch_eval)`` writing size, eval_loss, eval and its own keys
+    # into ``out`` from the fetched {name: float} - and adding to its ``*_total`` counters, so only for a step that completed.
+    def _ctc_criterion(self, logits, b, train):
         entry_b = None
         if self.delay_penalty is not None:
-            lo_d, hi_d = windows if self.align_window is not None else (None, None)
-            loss_b, entry_b, grad = ops.ctc_loss_delay(logits, flat_d, offs_d, seq_d, maxlen, self.delay_penalty, win_lo=lo_d,
-                                                       win_hi=hi_d, want_grad=train)
+            lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
+            loss_b, entry_b, grad = ops.ctc_loss_delay(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.delay_penalty,
+                                                       win_lo=lo_d, win_hi=hi_d, want_grad=train)
         elif self.align_window is not None:
-            loss_b, grad = ops.ctc_loss_windowed(logits, flat_d, offs_d, seq_d, maxlen, windows[0], windows[1],
+            loss_b, grad = ops.ctc_loss_windowed(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, b.windows[0], b.windows[1],
                                                  want_grad=train)
         else:
-            loss_b, grad = ops.ctc_loss(logits, flat_d, offs_d, seq_d, maxlen, want_grad=train)
-        out = {"size": size}
-        tokens = out_len = None
-        reg = None
-        if self.sm_weight > 0:                                                   # graph.py:120-133: loss += reg
-            T_, B_, V_ = logits.shape
-            reg = ops.label_smoothing(logits.view(T_ * B_, V_), self.sm_weight, self.sm_logq,
-                                      grad.view(T_ * B_, V_) if train else None)
-        kd = self._teacher_term(logits, seq_d, teacher, grad, train)
-        if pairs is not None:                              # teacher_weight is excluded: the two share kd's place in the word
-            kd = ops.consistency_loss(logits, pairs, grad_scale=0.5 * self.consistency_weight, grad=grad)[:3]
-        if fetch_eval:
-            tokens, out_len = ops.ctc_greedy(logits, seq_d)
-        bn_saved = None
-        if train:
-            bn_saved = dict(self.model.saved.get("bn") or {})
-            self._buckets = (dp.GradientBuckets(self.model.ps.grad, self.pg)
-                             if self.pg is not None and self.dp_buckets and (self.world > 1 or self._force_buckets) else None)
-            self.model.backward(grad, buckets=self._buckets)
-            self._apply_gradients()
-        # one device->host sync per step, like the reference's sess.run
-        if kd is None and entry_b is None:
-            eval_loss = float(loss_b.sum().item())                               # graph.py:116 reduce_sum
-        else:                                             # the same float32 sum, with the options' scalars in its copy
-            word = torch.cat([loss_b.sum().to(torch.float64).view(1)] + (self._kd_scalars(kd) if kd is not None else []) +
-                             (self._entry_scalars(loss_b, entry_b, offs_d, seq_d) if entry_b is not None else [])
-                             ).cpu().numpy()
-            eval_loss = float(word[0])
-        status = int(ops.lstm_status(dev).item())
-        if status != 0:
-            return None, status
-        if train and bn_saved:
-            self.model.update_moving_averages(bn_saved)   # batch-norm UPDATE_OPS (graph.py:194-196); only with use_bn
-        out["eval_loss"] = eval_loss
-        out["loss"] = eval_loss + (float(reg.item()) if reg is not None else 0.0)
-        if pairs is not None:
-            out["cr_loss"], out["cr_frames"], out["cr_agree"] = float(word[1]), int(word[2]), int(word[3])
-            self.cr_loss_total += out["cr_loss"]
-            self.cr_frames_total += out["cr_frames"]
-            self.cr_agree_total += out["cr_agree"]
-            out["loss"] += self.consistency_weight * 0.5 * out["cr_loss"]
-        elif kd is not None:
-            out["loss"] += self._kd_outputs(out, word[1:4])
-        if entry_b is not None:
-            out["entry_sum"], out["entry_labels"] = float(word[-2]), int(word[-1])
-            self.entry_sum_total += out["entry_sum"]
-            self.entry_labels_total += out["entry_labels"]
-        if fetch_eval:
-            tok, n = tokens.cpu().numpy(), out_len.cpu().numpy()
-            if flat_host is None:
-                flat_host, offs_host = flat_d.cpu().numpy(), offs_d.cpu().numpy()
-            if pairs is not None:                          # view a against the original labels: the first halves
-                B_ = pairs.numel()
-                tok, n, offs_host = tok[:B_], n[:B_], offs_host[:B_ + 1]
-                flat_host = flat_host[:offs_host[-1]]
-                out["eval_size"] = size // 2               # the labels ``eval`` was counted against
-            out["eval"] = float(ops.edit_distance_host(tok, n, flat_host, offs_host).sum())   # graph.py:143-150
-            out["decoded"] = (tok, n)
-        if fetch_logits:
-            out["logits"] = logits.permute(1, 0, 2).cpu().numpy()                # reference layout [B,T,V]
-        if train:
-            out["grad_norm"] = float(self.norm_out[0].item())
-        return out, 0
+            loss_b, grad = ops.ctc_loss(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, want_grad=train)
 
-    def _teacher_term(self, logits, seq_d, teacher, grad, train):
-        """teacher_weight on a base criterion: ``ops.kd_loss`` adding lambda * tau * (q - p) to the criterion's gradient
-        (loss only when not training).  None without the option."""
-        if self.teacher_weight is None:
-            return None
+        def scalars():
+            pairs = [("eval_loss", loss_b.sum())]                                # graph.py:116 reduce_sum, in float32
+            if entry_b is not None:
+                pairs += zip(("entry_sum", "entry_labels"), self._entry_scalars(loss_b, entry_b, b.offs_d, b.seq_d))
+            return pairs
+
+        def outputs(host, out, fetch_eval):                  # (``eval`` needs the greedy decode: the tail's)
+            out["size"], out["eval_loss"] = b.size, host["eval_loss"]
+            if entry_b is not None:
+                out["entry_sum"], out["entry_labels"] = host["entry_sum"], int(host["entry_labels"])
+                self.entry_sum_total += out["entry_sum"]
+                self.entry_labels_total += out["entry_labels"]
+        return grad, scalars, outputs
+
+    def _xent_criterion(self, logits, b, train):
+        """``size`` the scored frames, ``eval`` those the argmax gets wrong.  A batch without a scored frame (size 0) still
+        runs the optimizer step - on a zero loss gradient - so that ranks stay in lockstep (kd alike)."""
+        if b.frame_target is None:
+            raise ValueError("objective = xent needs frame_target (create_pipeline_sequence_batch(..., frame_targets=...))")
+        loss_b, frames, correct, grad = ops.xent_loss(logits, b.frame_target, b.seq_d, want_grad=train)
+
+        def outputs(host, out, fetch_eval):
+            out["size"], out["eval_loss"] = int(host["frames"]), host["eval_loss"]
+            if fetch_eval:
+                out["eval"] = float(out["size"] - int(host["correct"]))
+        return grad, lambda: zip(("eval_loss", "frames", "correct"), self._f64_sums((loss_b, frames, correct))), outputs
+
+    def _kd_criterion(self, logits, b, train):
+        """The distillation term alone (lambda = 1): ``size`` the scored frames, ``eval`` those whose two argmaxes disagree."""
         tau = self.teacher_temperature
-        return ops.kd_loss(logits, teacher[0], seq_d, teacher[1], temperature=tau, grad_scale=self.teacher_weight * tau,
-                           grad=grad if train else None, want_grad=False)[:3]
+        loss_b, frames, agree, grad = ops.kd_loss(logits, b.teacher[0], b.seq_d, b.teacher[1], temperature=tau, grad_scale=tau,
+                                                  want_grad=train)
+
+        def outputs(host, out, fetch_eval):
+            out["eval_loss"] = self._kd_outputs(out, host)
+            out["size"] = out["kd_frames"]
+            if fetch_eval:
+                out["eval"] = float(out["kd_frames"] - out["kd_agree"])
+        return grad, lambda: zip(self.KD_KEYS, self._f64_sums((loss_b, frames, agree))), outputs
+
+    @staticmethod
+    def _f64_sums(tensors):
+        return [t.to(torch.float64).sum() for t in tensors]
 
     @staticmethod
     def _entry_scalars(loss_b, entry_b, offs_d, seq_d):
@@ -639,106 +641,90 @@ class CTCGraph:
         n = (offs_d[1:] - offs_d[:-1]).to(torch.int64)
         ok = torch.isfinite(loss_b) & (seq_d > 0) & (n <= seq_d)
         zero = torch.zeros((), dtype=torch.float64, device=loss_b.device)
-        return [torch.where(ok, entry_b.to(torch.float64), zero).sum().view(1),
-                torch.where(ok, n, torch.zeros_like(n)).sum().to(torch.float64).view(1)]
+        return [torch.where(ok, entry_b.to(torch.float64), zero).sum(), torch.where(ok, n, torch.zeros_like(n)).sum()]
 
-    @staticmethod
-    def _kd_scalars(kd):
-        return [t.to(torch.float64).sum().view(1) for t in kd]
-
-    def _kd_outputs(self, out, word):
+    def _kd_outputs(self, out, host):
         """Writes kd_loss / kd_frames / kd_agree into ``out`` and returns what the term adds to ``loss``."""
         tau = self.teacher_temperature
-        out["kd_loss"], out["kd_frames"], out["kd_agree"] = float(word[0]), int(word[1]), int(word[2])
+        out["kd_loss"], out["kd_frames"], out["kd_agree"] = host["kd_loss"], int(host["kd_frames"]), int(host["kd_agree"])
         self.kd_frames_total += out["kd_frames"]
         self.kd_agree_total += out["kd_agree"]
         return (1.0 if self.teacher_weight is None else self.teacher_weight) * tau * tau * out["kd_loss"]
 
-    def _finish_kd(self, logits, seq_d, teacher, fetch_eval, fetch_logits, train):
-        """The rest of a step under objective = kd: ``ops.kd_loss`` in the place of ``ops.ctc_loss`` (lambda = 1);
-        regulariser, backward, L2, clip, optimizer and status word as in the CTC step.  A batch without a scored frame (size
-        0) still runs the optimizer step - on a zero loss gradient - so that ranks stay in lockstep."""
-        dev = self.model.device
-        tau = self.teacher_temperature
-        loss_b, frames, agree, grad = ops.kd_loss(logits, teacher[0], seq_d, teacher[1], temperature=tau, grad_scale=tau,
-                                                  want_grad=train)
-        reg = None
-        if self.sm_weight > 0:
-            T_, B_, V_ = logits.shape
-            reg = ops.label_smoothing(logits.view(T_ * B_, V_), self.sm_weight, self.sm_logq,
-                                      grad.view(T_ * B_, V_) if train else None)
-        bn_saved = None
-        if train:
-            bn_saved = dict(self.model.saved.get("bn") or {})
-            self._buckets = (dp.GradientBuckets(self.model.ps.grad, self.pg)
-                             if self.pg is not None and self.dp_buckets and (self.world > 1 or self._force_buckets) else None)
-            self.model.backward(grad, buckets=self._buckets)
-            self._apply_gradients()
-        # everything the host wants, in ONE device->host copy: the step's single sync
-        zero = torch.zeros(1, dtype=torch.float64, device=dev)
-        word = torch.cat(self._kd_scalars((loss_b, frames, agree, ops.lstm_status(dev))) +
-                         [reg.to(torch.float64).view(1) if reg is not None else zero,
-                          self.norm_out[:1].to(torch.float64) if train else zero]).cpu().numpy()
-        status = int(word[3])
-        if status != 0:
-            return None, status
-        if train and bn_saved:
-            self.model.update_moving_averages(bn_saved)
-        out = {}
-        out["eval_loss"] = self._kd_outputs(out, word[:3])
-        out["size"] = out["kd_frames"]
-        out["loss"] = out["eval_loss"] + float(word[4])
-        if fetch_eval:
-            out["eval"] = float(out["kd_frames"] - out["kd_agree"])      # frames whose two argmaxes disagree
-        if fetch_logits:
-            out["logits"] = logits.permute(1, 0, 2).cpu().numpy()
-        if train:
-            out["grad_norm"] = float(word[5])
-        return out, 0
+    def _new_buckets(self):
+        """The backward's per-layer gradient buckets (None: one all-reduce after it); ``_apply_gradients`` finishes them."""
+        self._buckets = (dp.GradientBuckets(self.model.ps.grad, self.pg)
+                         if self.pg is not None and self.dp_buckets and (self.world > 1 or self._force_buckets) else None)
+        return self._buckets
 
-    def _finish_xent(self, logits, seq_d, frame_target, fetch_eval, fetch_logits, train, teacher=None):
-        """The rest of a step under objective = xent: ``ops.xent_loss`` in the place of ``ops.ctc_loss``; regulariser,
-        backward, L2, clip, optimizer and status word as in the CTC step.  A batch without a scored frame (size 0) still
-        runs the optimizer step - on a zero loss gradient - so that ranks stay in lockstep."""
-        if frame_target is None:
-            raise ValueError("objective = xent needs frame_target (create_pipeline_sequence_batch(..., frame_targets=...))")
-        dev = self.model.device
-        loss_b, frames, correct, grad = ops.xent_loss(logits, frame_target, seq_d, want_grad=train)
-        reg = None
-        if self.sm_weight > 0:
-            T_, B_, V_ = logits.shape
+    def _finish_step(self, logits, b, fetch_eval, fetch_logits, train):
+        """What follows the forward in ``_step_once``, for every objective: criterion, the terms that share its gradient
+        buffer - in this order, the bits depend on it - backward, optimizer, the step's ONE device-to-host copy."""
+        criterion = {"ctc": self._ctc_criterion, "xent": self._xent_criterion, "kd": self._kd_criterion}[self.objective]
+        grad, scalars, outputs = criterion(logits, b, train)
+        T_, B_, V_ = logits.shape
+        reg = kd = cr = tokens = None
+        if self.sm_weight > 0:                                                   # graph.py:120-133: loss += reg
             reg = ops.label_smoothing(logits.view(T_ * B_, V_), self.sm_weight, self.sm_logq,
                                       grad.view(T_ * B_, V_) if train else None)
-        kd = self._teacher_term(logits, seq_d, teacher, grad, train)
+        if self.teacher_weight is not None:       # lambda * tau * (q - p) into the criterion's gradient (train=False: loss only)
+            tau = self.teacher_temperature
+            kd = ops.kd_loss(logits, b.teacher[0], b.seq_d, b.teacher[1], temperature=tau,
+                             grad_scale=self.teacher_weight * tau, grad=grad if train else None, want_grad=False)[:3]
+        if b.pairs is not None:                                                  # (teacher_weight is excluded)
+            cr = ops.consistency_loss(logits, b.pairs, grad_scale=0.5 * self.consistency_weight, grad=grad)[:3]
+        if fetch_eval and self.objective == "ctc":
+            tokens, out_len = ops.ctc_greedy(logits, b.seq_d)
         bn_saved = None
         if train:
             bn_saved = dict(self.model.saved.get("bn") or {})
-            self._buckets = (dp.GradientBuckets(self.model.ps.grad, self.pg)
-                             if self.pg is not None and self.dp_buckets and (self.world > 1 or self._force_buckets) else None)
-            self.model.backward(grad, buckets=self._buckets)
+            self.model.backward(grad, buckets=self._new_buckets())
             self._apply_gradients()
-        # everything the host wants, in ONE device->host copy: the step's single sync
-        f64 = lambda t: t.to(torch.float64).sum().view(1)
-        zero = torch.zeros(1, dtype=torch.float64, device=dev)
-        word = torch.cat([f64(loss_b), f64(frames), f64(correct), f64(ops.lstm_status(dev)),
-                          reg.to(torch.float64).view(1) if reg is not None else zero,
-                          self.norm_out[:1].to(torch.float64) if train else zero] +
-                         (self._kd_scalars(kd) if kd is not None else [])).cpu().numpy()
-        status = int(word[3])
+        # everything the host wants, in ONE device->host copy: the step's single sync, like the reference's sess.run
+        word = _HostScalars()
+        for name, t in scalars():
+            word.add(name, t)
+        word.add("status", ops.lstm_status(self.model.device))
+        if reg is not None:
+            word.add("reg", reg)
+        if train:
+            word.add("grad_norm", self.norm_out[:1])
+        for keys, term in ((self.KD_KEYS, kd), (self.CR_KEYS, cr)):
+            for name, t in zip(keys, self._f64_sums(term or ())):
+                word.add(name, t)
+        host = word.fetch()
+        status = int(host["status"])
         if status != 0:
             return None, status
         if train and bn_saved:
-            self.model.update_moving_averages(bn_saved)
-        n_frames = int(word[1])
-        out = {"size": n_frames, "eval_loss": float(word[0]), "loss": float(word[0]) + float(word[4])}
-        if kd is not None:
-            out["loss"] += self._kd_outputs(out, word[6:9])
-        if fetch_eval:
-            out["eval"] = float(n_frames - int(word[2]))          # frames the argmax gets wrong
+            self.model.update_moving_averages(bn_saved)   # batch-norm UPDATE_OPS (graph.py:194-196); only with use_bn
+        out = {}
+        outputs(host, out, fetch_eval)
+        out["loss"] = out["eval_loss"] + host.get("reg", 0.0)
+        if cr is not None:
+            out["cr_loss"], out["cr_frames"], out["cr_agree"] = host["cr_loss"], int(host["cr_frames"]), int(host["cr_agree"])
+            self.cr_loss_total += out["cr_loss"]
+            self.cr_frames_total += out["cr_frames"]
+            self.cr_agree_total += out["cr_agree"]
+            out["loss"] += self.consistency_weight * 0.5 * out["cr_loss"]
+        elif kd is not None:
+            out["loss"] += self._kd_outputs(out, host)
+        if tokens is not None:
+            tok, n = tokens.cpu().numpy(), out_len.cpu().numpy()
+            flat, offs = b.flat, b.offs
+            if flat is None:
+                flat, offs = b.flat_d.cpu().numpy(), b.offs_d.cpu().numpy()
+            if b.pairs is not None:                        # view a against the original labels: the first halves
+                B_ = b.pairs.numel()
+                tok, n, offs = tok[:B_], n[:B_], offs[:B_ + 1]
+                flat = flat[:offs[-1]]
+                out["eval_size"] = b.size // 2             # the labels ``eval`` was counted against
+            out["eval"] = float(ops.edit_distance_host(tok, n, flat, offs).sum())   # graph.py:143-150
+            out["decoded"] = (tok, n)
         if fetch_logits:
-            out["logits"] = logits.permute(1, 0, 2).cpu().numpy()
+            out["logits"] = logits.permute(1, 0, 2).cpu().numpy()                # reference layout [B,T,V]
         if train:
-            out["grad_norm"] = float(word[5])
+            out["grad_norm"] = host["grad_norm"]
         return out, 0
 
     # ------------------------------------------------------------------------------------------------- forced alignment
@@ -760,23 +746,9 @@ class CTCGraph:
                 res = ops.ctc_align(logits, flat_d, offs_d, seq_d, maxlen)
                 return res, int(ops.lstm_status(dev).item())
 
-            if self._fallback.latched:
-                with ops.force_launch_train():
-                    res, status = run()
-            else:
-                res, status = run()
-                if status == 0:
-                    self._fallback.good()
-                else:                                      # a persistent launch could not complete: launch train
-                    self.persist_fallbacks += 1
-                    self._fallback.failed(status, self.persist_fallbacks)
-                    with ops.force_launch_train():
-                        res, status = run()
-            if status != 0:
-                raise RuntimeError("LSTM recurrence failed on the launch train as well (status %d)" % status)
+            ali, lidx, score = self._fallback.run(run)
         finally:
             model.is_training, model.keep = mode
-        ali, lidx, score = res
         return {"ali": ali.cpu().numpy(), "label_index": lidx.cpu().numpy(), "score": score.cpu().numpy(),
                 "sequence_length": seq}
 
@@ -814,9 +786,10 @@ class InferenceGraph:
         self.pipeline = pipeline
         self.model = Model(cfg, device)
         self.smooth = smooth_factor
-        self.persist_fallbacks = 0
         self._fallback = _FallbackLatch()
         self.keys = ["filename", "nnet_input", "sequence_length", "logits", "nnet_output"]
+
+    persist_fallbacks = property(lambda self: self._fallback.total, doc=CTCGraph.persist_fallbacks.__doc__)
 
     def __getitem__(self, key):
         if key not in self.keys:
@@ -840,21 +813,7 @@ class InferenceGraph:
             out = self.model.forward(xd, sd)
             return out, int(ops.lstm_status(dev).item())
 
-        if self._fallback.latched:
-            with ops.force_launch_train():
-                logits, status = run()
-        else:
-            logits, status = run()
-            if status == 0:
-                self._fallback.good()
-            else:                                          # a persistent launch could not complete: launch train
-                self.persist_fallbacks += 1
-                self._fallback.failed(status, self.persist_fallbacks)
-                with ops.force_launch_train():
-                    logits, status = run()
-        if status != 0:
-            raise RuntimeError("LSTM recurrence failed on the launch train as well")
-        return logits, seq
+        return self._fallback.run(run, error="LSTM recurrence failed on the launch train as well"), seq
 
     def restore(self, path):
         load_params(self.model.ps, path)
