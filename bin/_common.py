@@ -187,6 +187,32 @@ def report_delay_penalty(graph):
                % (graph.delay_penalty, graph.entry_sum_total / max(n, 1), n))
 
 
+def entropy_keywords(args):
+    """--entropy-weight: the graph keyword, empty without the flag (nnet-init has none).  The FATAL line and exit 1 when the
+    value is negative or not finite, meets another objective than ctc, or comes with --delay-penalty.  Host work only: runs
+    BEFORE the device is set up."""
+    weight = getattr(args, 'entropy_weight', None)
+    if weight is None:
+        return {}
+    import math
+    if not (math.isfinite(weight) and weight >= 0):
+        _fatal('--entropy-weight must be a finite number >= 0, got %r' % weight)
+    if args.objective != 'ctc':
+        _fatal('--entropy-weight regularises the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
+    if getattr(args, 'delay_penalty', None) is not None:
+        _fatal('--entropy-weight does not combine with --delay-penalty (the entropy of the tilted path posterior is not built)')
+    return {'entropy_weight': weight}
+
+
+def report_entropy_weight(graph):
+    """One INFO line at the end of a pass under --entropy-weight: the entropy of the posterior over the feasible paths, in
+    nats per utterance-frame."""
+    from lstm_ctc_amd.nnet import tflog
+    n = graph.path_entropy_frames_total
+    tflog.info('entropy weight %g: mean path entropy %.6f nats per frame over %d frame(s)'
+               % (graph.entropy_weight, graph.path_entropy_total / max(n, 1), n))
+
+
 def spec_augment_keywords(args):
     """--spec-augment: the graph keyword, empty without the flag.  The FATAL line and exit 1 for a value that
     nnet.augment.parse_spec refuses, and for bins that do not divide the input_dim of a readable <nnet-config>.  Host work
@@ -311,6 +337,10 @@ FLAGS = {
     '--delay-penalty': dict(type=float, default=None, help='with --objective ctc: weight every path by exp(-penalty * sum of the '
                             'frames at which its labels are entered), so that the model learns to emit earlier (new); needs no '
                             'table, composes with --align-window; 0 is plain CTC and reports the mean label entry frame'),
+    '--entropy-weight': dict(type=float, default=None, help='with --objective ctc: maximum-entropy CTC (new): subtract weight * '
+                             'the entropy of the posterior over the feasible paths from the CTC loss, so that the model does not '
+                             'collapse onto a few spiky alignments; needs no table, composes with --align-window, not with '
+                             '--delay-penalty; 0 is plain CTC and reports the mean path entropy in nats per frame'),
     '--spec-augment': dict(type=str, default=None, help='SpecAugment on the device, training steps only (new): '
                            'time=NxW,freq=NxW,bins=F[,cap=P][,fill=V] = N time masks of at most W raw frames (and at most P percent '
                            'of the utterance, default 100), N frequency masks of at most W of the F bins of a feature group '

@@ -141,6 +141,37 @@ int lc_ctc_loss_delay(const float *logits, int T, int B, int V, const int *label
                       float *loss, float *entry_sum, float *grad, void *workspace, size_t workspace_bytes,
                       lc_stream_t stream);
 
+/* Maximum-entropy CTC (EnCTC; Liu, Jin and Zhang, NeurIPS 2018): the CTC loss, the entropy of the posterior over the feasible
+ * paths, and the gradient of loss - entropy_weight * entropy.  No reference counterpart.  Everything not said here is
+ * lc_ctc_loss_windowed's contract (blank = V-1, ctc_merge_repeated transitions, a path starts in position 0 or 1 and ends in
+ * S-1 or S-2).  With log p(pi) = sum_t log_softmax(logits[t,b,:])[pi_t], Z = sum_pi p(pi) over the feasible paths and
+ * Ebar = sum_pi (p(pi) / Z) log p(pi):
+ *   win_lo, win_hi  both NULL = unconstrained; else lc_ctc_loss_windowed's windows (exactly one NULL is LC_EINVAL);
+ *   entropy_weight  eta, any finite value (not finite -> LC_EINVAL); it enters the gradient only;
+ *   loss [B]        -log Z, natural log: exactly lc_ctc_loss_windowed's loss with windows and lc_ctc_loss_delay's at
+ *                   delay_penalty 0 without, bit for bit;
+ *   entropy [B]     required: H = -sum_pi (p / Z) log(p / Z) = log Z - Ebar in nats; >= 0, +0 exactly when one path survives;
+ *   grad [T,B,V]    or NULL: d (loss - eta H) / d logits, the exact derivative (nothing is held constant) =
+ *                   softmax - sum_{s: class(s) = k} occupancy(t, s) (1 + eta (Ebar - c(t, s))), c(t, s) the mean of log p(pi)
+ *                   over the posterior restricted to the paths through (t, s); live rows still sum to 0; +0 for
+ *                   t >= seq_len[b].  With entropy_weight 0 it is those siblings' grad, bit for bit.
+ * lc_ctc_loss's conventions: a skipped utterance -> loss 0, entropy 0, gradient 0; a bad label -> loss NaN, entropy NaN,
+ * gradient 0; no surviving path -> loss +inf, entropy 0, gradient = softmax, no NaN anywhere; L = 0 -> the all-blank path,
+ * entropy +0.  Every element of every output is written on every call; results are bit-identical from call to call and
+ * loss / entropy are bit-identical with and without a gradient (no atomics, fixed summation orders).  Without a gradient
+ * only the forward sweep runs.  Arithmetic: lc_ctc_loss_windowed's cells, and beside each cell a double m = the mean of
+ * log2 p over the prefixes that end in it (the expectation semiring's second component): emission + the mean of the
+ * predecessors' m under the weights the cell's log-sum-exp forms, taken relative to the heaviest predecessor's m, so that
+ * the error is a few fp32 ulps of the spread of the m, not of their size, and a single path is carried exactly; m is a
+ * plain number, 0 in a dead cell.  Ebar, H = (log2 Z - Ebar) ln 2 and the gradient's occupancy * (Ebar - c) terms (each
+ * formed as that product, summed per class in the plain gradient's order) are in double and rounded once.
+ * Shapes and errors as for lc_ctc_loss_windowed; the workspace holds both lattices twice (cells and means). */
+size_t lc_ctc_entropy_workspace_bytes(int T, int B, int V, int max_label_len);
+int lc_ctc_loss_entropy(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                        const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
+                        float entropy_weight, float *loss, float *entropy, float *grad,
+                        void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* Frame-level softmax cross-entropy against one target symbol per frame - the objective that trains on what lc_ctc_align
  * writes.  No reference counterpart (the reference never finished frame-level training).
  *   logits [T,B,V] time-major fp32; targets [B,T] int32 (the layout of lc_ctc_align's ali); seq_len [B].

@@ -1,5 +1,5 @@
-// ctc_lattice.h — what the double-cell log2-domain CTC lattices share (ctc_lattice.hip: windowed and delay-penalised CTC,
-// ctc_align.hip: forced alignment; DESIGN.md sections 3.6, 3.8): the per-frame log-sum-exp kernel, -inf as "log zero", the
+// ctc_lattice.h — what the double-cell log2-domain CTC lattices share (ctc_lattice.hip: windowed, delay-penalised and
+// maximum-entropy CTC, ctc_align.hip: forced alignment; DESIGN.md sections 3.6, 3.8, 3.14): the per-frame log-sum-exp kernel, -inf as "log zero", the
 // log-sum-exp of a cell's predecessors on the fp32 exp2 / log2 pipes relative to their maximum, the DPP neighbour shift.
 #pragma once
 #include "common.h"
@@ -49,6 +49,38 @@ __device__ __forceinline__ double lat_shr1(double x)
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x138, 0xf, 0xf, false);
     const int hi = __builtin_amdgcn_update_dpp((int)0xfff00000, __double2hiint(x), 0x138, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
+}
+// the same shift for a quantity that is no logarithm: lane 0 receives 0
+__device__ __forceinline__ double lat_shr1_zero(double x)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x138, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x138, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// lat_lse2 / lat_lse3, bit for bit, and in ``mean`` the mean of ma, mb [, mc] under the same weights 2^(a_i - max) / sum:
+// the expectation semiring's second component (maximum-entropy CTC).  The mean is formed relative to the m of the maximal
+// operand, whose weight is exactly 1: its error is a few fp32 ulps of the SPREAD of the m_i, not of their magnitude, and a
+// cell with one live predecessor copies that predecessor's m exactly.  A "log zero" operand has weight 0 and must come with
+// a finite m (0 by convention); all operands dead gives a NaN mean, which the caller discards with the dead cell.
+__device__ __forceinline__ double lat_lse2_mean(double a, double b, double ma, double mb, double &mean)
+{
+    const double m = fmax(fmax(a, b), -DBL_MAX);
+    const float wa = __builtin_amdgcn_exp2f((float)(a - m)), wb = __builtin_amdgcn_exp2f((float)(b - m));
+    const float sum = wa + wb;
+    const double ref = a == m ? ma : mb;
+    mean = ref + ((double)wa * (ma - ref) + (double)wb * (mb - ref)) * (double)__builtin_amdgcn_rcpf(sum);
+    return m + (double)__builtin_amdgcn_logf(sum);
+}
+__device__ __forceinline__ double lat_lse3_mean(double a, double b, double c, double ma, double mb, double mc, double &mean)
+{
+    const double m = fmax(fmax(fmax(a, b), c), -DBL_MAX);
+    const float wa = __builtin_amdgcn_exp2f((float)(a - m)), wb = __builtin_amdgcn_exp2f((float)(b - m)),
+                wc = __builtin_amdgcn_exp2f((float)(c - m));
+    const float sum = wa + wb + wc;
+    const double ref = a == m ? ma : b == m ? mb : mc;
+    mean = ref + ((double)wa * (ma - ref) + (double)wb * (mb - ref) + (double)wc * (mc - ref)) *
+                     (double)__builtin_amdgcn_rcpf(sum);
+    return m + (double)__builtin_amdgcn_logf(sum);
 }
 __device__ __forceinline__ double lat_readlane(double x, int lane)
 {

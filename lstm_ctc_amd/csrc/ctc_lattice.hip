@@ -1,4 +1,5 @@
-// ctc_lattice.hip — the two CTC criteria that sum over a constrained or re-weighted set of paths, on one lattice:
+// ctc_lattice.hip — the three CTC criteria that sum over a constrained or re-weighted set of paths, or carry a second quantity
+// along them, on one lattice:
 //   * alignment-windowed CTC (lc_ctc_loss_windowed): the CTC loss and gradient summed only over the paths that keep every label
 //     inside a window of frames (Senior et al. 2015: windows around a forced alignment stop a unidirectional model emitting
 //     late).  DESIGN.md section 3.8.
@@ -6,13 +7,16 @@
 //     E = sum over the labels of the frame at which the label's run starts, plus E's expectation under that tilted posterior
 //     (entry_sum: the "expected frame at which a label is entered", summed over the labels), with optional label windows.
 //     DESIGN.md section 3.10.
+//   * maximum-entropy CTC (lc_ctc_loss_entropy, Liu et al. 2018): the (windowed) CTC loss, the entropy H = log Z - Ebar of the
+//     posterior over the feasible paths (Ebar = the posterior mean of log p(path)), and the exact gradient of loss - eta H,
+//     with optional label windows.  DESIGN.md section 3.14.
 // No reference counterpart.  lc_ctc_loss (ctc.hip) is not touched by this file.
 //
 // Contract (include/lstm_ctc_hip.h): lc_ctc_loss's, plus win_lo / win_hi parallel to the flat labels.  Label j may sit on
 // frame t only when win_lo[j] <= t <= win_hi[j]; blank positions are never constrained.
 //
-// Both entries run lat_launch: lse, [index], sweep, [grad<ENTRY> | entry], [fold] - four launches for the windowed loss (two
-// without a gradient).  No LDS atomics, no global atomics, every sum in a fixed order - the result is bit-identical from call
+// All entries run lat_launch: lse, [index], sweep, [grad<ENTRY, ENT> | entry], [fold] - four launches for the windowed and the
+// entropy loss (two without a gradient).  No LDS atomics, no global atomics, every sum in a fixed order - the result is bit-identical from call
 // to call:
 //   1. lat_lse_kernel        (ctc_lattice.h) one wave per live frame (t, b): lse[t, b] = log sum_k exp(logits[t, b, k]), fp32.
 //   2. lat_index_kernel      (gradient only) one workgroup per utterance: the label indices ordered by (class, index), and per
@@ -43,12 +47,21 @@
 //          position of the previously processed row t + 1 carries w(t + 1).  (Out of an odd position p - 1 into the blank p,
 //          or out of the odd p - 2 into the odd p; the move p - 1 -> p into an odd p leaves a blank and carries nothing.)
 //        * the windows may be NULL (no constraint).
-//   4. lat_grad_kernel<ENTRY>  one wave per frame.  occupancy(t, s) = 2^(alpha + beta - emission - log2 p), the exponent formed
+//      ENT (lc_ctc_loss_entropy; the other instantiations carry none of it): the expectation semiring.  Beside each cell a the
+//      sweep keeps m, the mean of log2 p(prefix) over the prefixes that end in the cell under their posterior:
+//      m = emission + sum_i w_i m_i / sum_i w_i over the cell's predecessors, w_i = 2^(a_i - max) the terms its log-sum-exp
+//      forms (lat_lse2_mean / lat_lse3_mean, ctc_lattice.h: the mean relative to the heaviest predecessor's m).  m is a plain
+//      double, 0 in a dead cell by a select; its rows go to the workspace beside the cells'.  Direction 0 finishes with Ebar
+//      (the end cells' means under the weights of log2 p, to the workspace) and H = (log2 p - Ebar) ln 2 >= 0, in double,
+//      rounded once; a single path gives m == a bit for bit and H = +0.  The windows may be NULL.
+//   4. lat_grad_kernel<ENTRY, ENT>  one wave per frame.  occupancy(t, s) = 2^(alpha + beta - emission - log2 p), the exponent formed
 //      in double; lane k sums the positions of class k, k + 64, ... in the order of lat_index_kernel's list, the blank's
 //      positions are summed lane by lane and then by the wave's DPP reduction.  grad = softmax - occupancy.  ENTRY also sums
 //      occupancy(t, s) * notyet(s), notyet(s) = L - (s + 1) / 2, per frame in double (each lane its positions in sequence,
 //      then a fixed butterfly) into the workspace; without a gradient lat_entry_kernel does the same from the two lattices
-//      alone.
+//      alone.  ENT subtracts eta * ln 2 * sum occupancy(t, s) * (Ebar - c(t, s)), c = m_alpha + m_beta - emission the mean log2
+//      probability of the paths through the cell, from the plain gradient: the plain part is summed as without ENT, the
+//      products beside it in double in the same orders.
 //   5. lat_fold_kernel       (entry_sum only) one wave per utterance folds its frame terms in a fixed order in double and rounds
 //      once.
 // The band (only positions whose window contains t are live) is NOT exploited: every position is computed on every frame.
@@ -104,8 +117,9 @@ __global__ __launch_bounds__(256) void lat_index_kernel(int V, const int *__rest
 }
 
 // ------------------------------------------------------------------------------------------ 3. alpha / beta sweeps
-// DELAY = false: win_lo / win_hi are not NULL (the host checks) and lambda is not read.
-template <int PPL, bool DELAY>
+// DELAY = ENT = false: win_lo / win_hi are not NULL (the host checks).  lambda is read by DELAY alone; malpha / mbeta / ebar /
+// entropy by ENT alone (nullptr otherwise).
+template <int PPL, bool DELAY, bool ENT>
 __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__ logits, int T, int B, int V,
                                                        const int *__restrict__ labels, const int *__restrict__ offs,
                                                        const int *__restrict__ seq_len, int maxL,
@@ -113,7 +127,9 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
                                                        float lambda, const float *__restrict__ lse,
                                                        double *__restrict__ alpha, double *__restrict__ beta, int srow,
                                                        int want_beta, float *__restrict__ loss,
-                                                       double *__restrict__ lp2, int *__restrict__ status)
+                                                       double *__restrict__ lp2, int *__restrict__ status,
+                                                       double *__restrict__ malpha, double *__restrict__ mbeta,
+                                                       double *__restrict__ ebar, float *__restrict__ entropy)
 {
     constexpr int K = PPL <= 4 ? 8 : 32 / PPL;            // frames fetched ahead as one chunk: 8, 8, 8, 4, 2, 1
     constexpr int NG = PPL == 1 ? 1 : PPL / 2;            // label positions (gathers, windows) per lane
@@ -124,7 +140,10 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
     const int blank = V - 1;
     const double NEG = lat_neg_inf();
     if (Tb == 0 || L > Tb) {                              // lc_ctc_loss: the utterance is skipped, loss 0, gradient 0
-        if (lane == 0 && dir == 0) { loss[b] = 0.0f; lp2[b] = 0.0; status[b] = LAT_ZERO; }
+        if (lane == 0 && dir == 0) {
+            loss[b] = 0.0f; lp2[b] = 0.0; status[b] = LAT_ZERO;
+            if (ENT) { entropy[b] = 0.0f; ebar[b] = 0.0; }
+        }
         return;
     }
     {   // a label outside [0, V-1) (or a label count the workspace was not sized for): NaN loss, zero gradient, and the labels
@@ -136,7 +155,10 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
                 bad |= (lab < 0 || lab >= blank) ? 1 : 0;
             }
         if (__builtin_amdgcn_ballot_w64(bad != 0) != 0) {
-            if (lane == 0 && dir == 0) { loss[b] = __int_as_float(0x7fc00000); lp2[b] = 0.0; status[b] = LAT_NAN; }
+            if (lane == 0 && dir == 0) {
+                loss[b] = __int_as_float(0x7fc00000); lp2[b] = 0.0; status[b] = LAT_NAN;
+                if (ENT) { entropy[b] = __int_as_float(0x7fc00000); ebar[b] = 0.0; }
+            }
             return;
         }
     }
@@ -152,7 +174,7 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
             if ((p & 1) && p < S) {
                 const int i = dir ? L - 1 - (p >> 1) : (p >> 1);          // the label this position stands for
                 sym = labels[off + i];
-                if (!DELAY || win_lo) {
+                if (!(DELAY || ENT) || win_lo) {
                     lo = win_lo[off + i];
                     hi = win_hi[off + i];
                 }
@@ -167,6 +189,11 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
 #pragma unroll
     for (int j = 0; j < PPL; ++j) a[j] = NEG;
     if (lane == 0) a[0] = 0.0;                            // "before the first frame": it reaches positions 0 (stay) and 1
+    // ENT: mm[j] = the mean of log2 p(prefix) over the prefixes that end in the cell, under their posterior; 0 in a dead cell
+    constexpr int PM = ENT ? PPL : 1;
+    double mm[PM];
+#pragma unroll
+    for (int j = 0; j < PM; ++j) mm[j] = 0.0;
     const double wl = DELAY ? -(double)lambda * LAT_LOG2E_D : 0.0;       // w(t) = wl * t
 
     float cg[K][NG], cb[K], cl[K], ng[K][NG], nb[K], nl[K];
@@ -185,6 +212,7 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
     };
     fetch(0, cg, cb, cl);
     double *rows = (dir ? beta : alpha) + (size_t)b * T * srow;
+    double *mrows = ENT ? (dir ? mbeta : malpha) + (size_t)b * T * srow : nullptr;
     for (int k0 = 0; k0 < Tb; k0 += K) {
         fetch(k0 + K, ng, nb, nl);
 #pragma unroll
@@ -201,14 +229,32 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
                 const double w1odd = dir ? 0.0 : w, w1even = dir ? w : 0.0;
                 const double in1 = lat_shr1(a[PPL - 1]);
                 const double in2 = PPL == 1 ? lat_shr1(in1) : in1;           // s-2 of the lane's first label position
+                const double mi1 = ENT ? lat_shr1_zero(mm[PM - 1]) : 0.0;    // ENT: the neighbours' means, 0 into lane 0
+                const double mi2 = ENT && PPL == 1 ? lat_shr1_zero(mi1) : mi1;
 #pragma unroll
                 for (int j = PPL - 1; j >= 0; --j) {                         // descending: a[j-1], a[j-2] are the old frame's
                     const double p1 = j >= 1 ? a[j - 1] : in1;
                     const int g_ = PPL == 1 ? 0 : j >> 1;
-                    double v;
+                    double v, mean = 0.0;
                     float e = eb;
                     bool live = (valid >> j & 1u) != 0;
-                    if (PPL == 1) {
+                    if constexpr (ENT) {                                     // the same cells, and the means beside them
+                        const double q1 = j >= 1 ? mm[j - 1] : mi1;
+                        if (PPL == 1) {
+                            const bool two = (allow2 & 1u) != 0;
+                            v = lat_lse3_mean(a[0], p1, two ? in2 : NEG, mm[0], q1, two ? mi2 : 0.0, mean);
+                            if (lane & 1) e = (cg[k][0] - lz) * LAT_LOG2E;
+                            live = live && t >= wlo[0] && t <= whi[0];
+                        } else if (j & 1) {
+                            const bool two = (allow2 >> j & 1u) != 0;
+                            const double p2 = j >= 2 ? a[j - 2] : in2, q2 = j >= 2 ? mm[j - 2] : mi2;
+                            v = lat_lse3_mean(a[j], p1, two ? p2 : NEG, mm[j], q1, two ? q2 : 0.0, mean);
+                            e = (cg[k][g_] - lz) * LAT_LOG2E;
+                            live = live && t >= wlo[g_] && t <= whi[g_];
+                        } else {
+                            v = lat_lse2_mean(a[j], p1, mm[j], q1, mean);
+                        }
+                    } else if (PPL == 1) {
                         const double p2 = (allow2 & 1u) ? (DELAY ? in2 + w : in2) : NEG;
                         v = lat_lse3(a[0], DELAY ? p1 + ((lane & 1) ? w1odd : w1even) : p1, p2);
                         if (lane & 1) e = (cg[k][0] - lz) * LAT_LOG2E;
@@ -223,16 +269,20 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
                         v = lat_lse2(a[j], DELAY ? p1 + w1even : p1);        // blanks are never entered from s-2
                     }
                     a[j] = live ? v + (double)e : NEG;
+                    if constexpr (ENT) mm[j] = a[j] > NEG ? mean + (double)e : 0.0;      // dead: 0 by a select, also for a NaN mean
                 }
                 // the row
                 double *dst = rows + (size_t)t * srow;
                 if constexpr (PPL == 1) {
                     dst[lane] = a[0];                                        // srow >= 64
+                    if constexpr (ENT) mrows[(size_t)t * srow + lane] = mm[0];
                 } else {
 #pragma unroll
                     for (int c = 0; c < PPL / 2; ++c) {
                         const int p0 = lane * PPL + 2 * c;                   // srow is a multiple of 64: both or none
                         if (p0 < srow) *(double2 *)(dst + p0) = make_double2(a[2 * c], a[2 * c + 1]);
+                        if constexpr (ENT)
+                            if (p0 < srow) *(double2 *)(mrows + (size_t)t * srow + p0) = make_double2(mm[2 * c], mm[2 * c + 1]);
                     }
                 }
             }
@@ -256,14 +306,37 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
     }
     const double v1 = lat_readlane(m1, s1 / PPL);
     const double v2 = s2 >= 0 ? lat_readlane(m2, s2 / PPL) : NEG;
+    double u1 = 0.0, u2 = 0.0;                                               // ENT: the two end cells' means
+    if constexpr (ENT) {
+        double n1 = 0.0, n2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < PPL; ++j) {
+            if (j == (s1 & (PPL - 1))) n1 = mm[j];
+            if (s2 >= 0 && j == (s2 & (PPL - 1))) n2 = mm[j];
+        }
+        u1 = lat_readlane(n1, s1 / PPL);
+        u2 = s2 >= 0 ? lat_readlane(n2, s2 / PPL) : 0.0;
+    }
     if (lane == 0) {
         const double hi = fmax(v1, v2), lo = fmin(v1, v2);
         if (!(hi > NEG)) {                                                   // no surviving path
             loss[b] = INFINITY; lp2[b] = 0.0; status[b] = LAT_NOPATH;
+            if constexpr (ENT) { entropy[b] = 0.0f; ebar[b] = 0.0; }
         } else {
-            const double lp = hi + (double)__builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f((float)(lo - hi)));
+            const float wlo = __builtin_amdgcn_exp2f((float)(lo - hi));
+            const double lp = hi + (double)__builtin_amdgcn_logf(1.0f + wlo);
             loss[b] = (float)(0.0 - lp * LAT_LN2);
             lp2[b] = lp; status[b] = LAT_OK;
+            if constexpr (ENT) {
+                // Ebar = the mean of log2 p(path) under the path posterior: the end cells' means under the weights of lp, again
+                // relative to the heavier cell; H = (log2 Z - Ebar) ln 2 >= 0, formed in double and rounded once.  One path:
+                // its cells and its means are the same sums of the same emissions, and H is +0 exactly.
+                const double uhi = v1 >= v2 ? u1 : u2, ulo = v1 >= v2 ? u2 : u1;
+                const double eb2 = uhi + (double)wlo * (ulo - uhi) / (1.0 + (double)wlo);
+                const double h = (lp - eb2) * LAT_LN2;
+                ebar[b] = eb2;
+                entropy[b] = h > 0.0 ? (float)h : 0.0f;
+            }
         }
     }
 }
@@ -280,7 +353,11 @@ __device__ __forceinline__ double lat_wave_sum_d(double x)
 }
 
 // ------------------------------------------------------------------------------------------ 4. gradient (+ entry terms)
-template <bool ENTRY>
+// ENT (maximum-entropy CTC; never with ENTRY): the gradient of loss - eta H is the plain one minus eta times
+// sum_s occupancy(t, s) * (Ebar - c(t, s)), c = malpha + mbeta - emission the mean log-probability of the paths through the
+// cell.  The plain part is summed exactly as without ENT (eta = 0 gives its bits); the products occupancy * (Ebar - c), each
+// formed as that product, are summed beside it in double in the same orders and the term is rounded once.
+template <bool ENTRY, bool ENT>
 __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__ logits, int T, int B, int V,
                                                        const int *__restrict__ offs, const int *__restrict__ seq_len,
                                                        const float *__restrict__ lse, const double *__restrict__ alpha,
@@ -288,7 +365,9 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
                                                        const double *__restrict__ lp2, const int *__restrict__ status,
                                                        const int *__restrict__ order, int pitch,
                                                        const int *__restrict__ first, const int *__restrict__ cnt,
-                                                       float *__restrict__ grad, double *__restrict__ fterm)
+                                                       float *__restrict__ grad, double *__restrict__ fterm,
+                                                       const double *__restrict__ malpha, const double *__restrict__ mbeta,
+                                                       const double *__restrict__ ebar, float eta)
 {
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -313,18 +392,26 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
     const double lp = lp2[b];
     const int blank = V - 1;
     double eacc = 0.0;                                                       // this lane's sum of occupancy * notyet
+    const double *MA = ENT ? malpha + bt * srow : nullptr, *MB = ENT ? mbeta + bt * srow : nullptr;
+    const double eb2 = ENT ? ebar[b] : 0.0, etal = ENT ? (double)eta * LAT_LN2 : 0.0;      // the means are in log2
     // the blank: positions 0, 2, .., 2L, lane l takes 2l, 2l + 128, ... in sequence, then the wave's fixed reduction
     const float eb = (x[blank] - lz) * LAT_LOG2E;
     {
         const double c = (double)eb + lp;
         float acc = 0.0f;
+        double dacc = 0.0;                                                   // ENT: sum of occupancy * (Ebar - c)
         for (int s = 2 * lane; s < S; s += 128) {
             const float o = __builtin_amdgcn_exp2f((float)((A[s] + Bt[S - 1 - s]) - c));
             acc += o;
             if (ENTRY) eacc += (double)o * (double)(L - (s >> 1));
+            if (ENT) dacc += (double)o * (eb2 - ((MA[s] + MB[S - 1 - s]) - (double)eb));
         }
         acc = lc_wave_sum(acc);
-        if (lane == 0) g[blank] = __builtin_amdgcn_exp2f(eb) - acc;
+        if (ENT) dacc = lat_wave_sum_d(dacc);
+        if (lane == 0) {
+            const float plain = __builtin_amdgcn_exp2f(eb) - acc;
+            g[blank] = ENT ? plain - (float)(etal * dacc) : plain;
+        }
     }
     // the labels: lane k sums the positions of class k in the order of the utterance's list
     const int *ord = order + (size_t)b * pitch;
@@ -334,13 +421,16 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
         const double c = (double)e + lp;
         const int r0 = fr[k], n = cn[k];
         float acc = 0.0f;
+        double dacc = 0.0;
         for (int r = 0; r < n; ++r) {
             const int i = ord[r0 + r], s = 2 * i + 1;
             const float o = __builtin_amdgcn_exp2f((float)((A[s] + Bt[S - 1 - s]) - c));
             acc += o;
             if (ENTRY) eacc += (double)o * (double)(L - 1 - i);
+            if (ENT) dacc += (double)o * (eb2 - ((MA[s] + MB[S - 1 - s]) - (double)e));
         }
-        g[k] = __builtin_amdgcn_exp2f(e) - acc;
+        const float plain = __builtin_amdgcn_exp2f(e) - acc;
+        g[k] = ENT ? plain - (float)(etal * dacc) : plain;
     }
     if (ENTRY) {
         eacc = lat_wave_sum_d(eacc);
@@ -400,12 +490,12 @@ __global__ __launch_bounds__(64) void lat_fold_kernel(const double *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------ host
-// the workspace: slabs in this order; only the delay entry has the frame terms
+// the workspace: slabs in this order; only the delay entry has the frame terms, only the entropy entry Ebar and the means
 struct LatLayout {
-    size_t lse, status, lp2, order, first, cnt, fterm, alpha, beta, total;
+    size_t lse, status, lp2, ebar, order, first, cnt, fterm, alpha, beta, malpha, mbeta, total;
     int ppl, srow, pitch;
 };
-inline LatLayout lat_layout(int T, int B, int V, int max_label_len, bool with_fterm)
+inline LatLayout lat_layout(int T, int B, int V, int max_label_len, bool with_fterm, bool with_means)
 {
     LatLayout m;
     const int S = 2 * max_label_len + 1;
@@ -417,46 +507,54 @@ inline LatLayout lat_layout(int T, int B, int V, int max_label_len, bool with_ft
     m.lse = o; o += lc_align256(TB * sizeof(float));
     m.status = o; o += lc_align256((size_t)B * sizeof(int));
     m.lp2 = o; o += lc_align256((size_t)B * sizeof(double));
+    m.ebar = o; o += with_means ? lc_align256((size_t)B * sizeof(double)) : 0;
     m.order = o; o += lc_align256((size_t)B * m.pitch * sizeof(int));
     m.first = o; o += lc_align256((size_t)B * V * sizeof(int));
     m.cnt = o; o += lc_align256((size_t)B * V * sizeof(int));
     m.fterm = o; o += with_fterm ? lc_align256(TB * sizeof(double)) : 0;
     m.alpha = o; o += lc_align256(TB * m.srow * sizeof(double));
     m.beta = o; o += lc_align256(TB * m.srow * sizeof(double));
+    m.malpha = o; o += with_means ? lc_align256(TB * m.srow * sizeof(double)) : 0;
+    m.mbeta = o; o += with_means ? lc_align256(TB * m.srow * sizeof(double)) : 0;
     m.total = o;
     return m;
 }
-inline size_t lat_workspace_bytes(int T, int B, int V, int max_label_len, bool with_fterm)
+inline size_t lat_workspace_bytes(int T, int B, int V, int max_label_len, bool with_fterm, bool with_means)
 {
     if (T <= 0 || B <= 0 || V < 2 || max_label_len < 0 || max_label_len > 1023) return 0;
-    return lat_layout(T, B, V, max_label_len, with_fterm).total;
+    return lat_layout(T, B, V, max_label_len, with_fterm, with_means).total;
 }
 
-// what tells the two entries apart on the host: the name in front of an error, the tags of the launches
+// what tells the three entries apart on the host: the criterion, the names in front of an error, the tags of the launches
 struct LatEntry {
-    bool delay;
-    const char *name, *lse, *index, *sweep, *grad, *entry, *fold;
+    bool delay, entropy;
+    const char *name, *weight, *lse, *index, *sweep, *grad, *entry, *fold;
 };
-const LatEntry LAT_WINDOW = {false, "lc_ctc_loss_windowed", "ctc_window_lse", "ctc_window_index", "ctc_window_sweep",
-                             "ctc_window_grad", "ctc_window_entry", "ctc_window_fold"};
-const LatEntry LAT_DELAY = {true, "lc_ctc_loss_delay", "ctc_delay_lse", "ctc_delay_index", "ctc_delay_sweep",
-                            "ctc_delay_grad", "ctc_delay_entry", "ctc_delay_fold"};
+const LatEntry LAT_WINDOW = {false, false, "lc_ctc_loss_windowed", "delay_penalty", "ctc_window_lse", "ctc_window_index",
+                             "ctc_window_sweep", "ctc_window_grad", "ctc_window_entry", "ctc_window_fold"};
+const LatEntry LAT_DELAY = {true, false, "lc_ctc_loss_delay", "delay_penalty", "ctc_delay_lse", "ctc_delay_index",
+                            "ctc_delay_sweep", "ctc_delay_grad", "ctc_delay_entry", "ctc_delay_fold"};
+const LatEntry LAT_ENTROPY = {false, true, "lc_ctc_loss_entropy", "entropy_weight", "ctc_entropy_lse", "ctc_entropy_index",
+                              "ctc_entropy_sweep", "ctc_entropy_grad", "ctc_entropy_entry", "ctc_entropy_fold"};
 
-// The windowed entry comes with windows, delay_penalty 0 and no entry_sum.
+// ``weight`` is the delay penalty or the entropy weight, ``extra`` entry_sum [B] (delay; optional) or entropy [B] (entropy;
+// required).  The windowed entry comes with windows, weight 0 and no extra.
 int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
-               const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi, float delay_penalty, float *loss,
-               float *entry_sum, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream)
+               const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi, float weight, float *loss,
+               float *extra, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    LC_CHECK_ARG(logits && labels && label_offsets && seq_len && loss && workspace && (e.delay || (win_lo && win_hi)),
+    float *entry_sum = e.entropy ? nullptr : extra, *entropy = e.entropy ? extra : nullptr;
+    LC_CHECK_ARG(logits && labels && label_offsets && seq_len && loss && workspace && (!e.entropy || entropy) &&
+                     (e.delay || e.entropy || (win_lo && win_hi)),
                  "%s: null pointer", e.name);
     LC_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr), "%s: win_lo and win_hi go together (both or none)", e.name);
     LC_CHECK_ARG(T > 0 && B > 0 && V >= 2 && max_label_len >= 0, "%s: bad shape T=%d B=%d V=%d L=%d", e.name, T, B, V,
                  max_label_len);
     LC_CHECK_ARG(max_label_len <= 1023, "%s: label length %d exceeds the supported maximum 1023", e.name, max_label_len);
-    LC_CHECK_ARG(isfinite(delay_penalty), "%s: delay_penalty must be finite, got %g", e.name, (double)delay_penalty);
+    LC_CHECK_ARG(isfinite(weight), "%s: %s must be finite, got %g", e.name, e.weight, (double)weight);
     LC_CHECK_ARG((long long)B * 2 <= 0x7fffffffLL && ((long long)T * B + 3) / 4 <= 0x7fffffffLL,
                  "%s: T * B = %lld is beyond the launch grid", e.name, (long long)T * B);
-    const LatLayout m = lat_layout(T, B, V, max_label_len, e.delay);
+    const LatLayout m = lat_layout(T, B, V, max_label_len, e.delay, e.entropy);
     if (workspace_bytes < m.total) {
         lc_set_error("%s: workspace too small (%zu < %zu)", e.name, workspace_bytes, m.total);
         return LC_EWORKSPACE;
@@ -469,6 +567,7 @@ int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, cons
     int *order = (int *)(w + m.order), *first = (int *)(w + m.first), *cnt = (int *)(w + m.cnt);
     double *fterm = (double *)(w + m.fterm);             // only with entry_sum, which only the delay entry has
     double *alpha = (double *)(w + m.alpha), *beta = (double *)(w + m.beta);
+    double *ebar = (double *)(w + m.ebar), *malpha = (double *)(w + m.malpha), *mbeta = (double *)(w + m.mbeta);   // entropy only
     const unsigned frame_blocks = (unsigned)(((long long)T * B + 3) / 4);
     hipLaunchKernelGGL(lat_lse_kernel, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, seq_len, lse);
     LC_CHECK_LAUNCH(e.lse);
@@ -477,39 +576,51 @@ int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, cons
                            first, cnt);
         LC_CHECK_LAUNCH(e.index);
     }
-#define LC_LAT(PPL, DELAY)                                                                                              \
-    hipLaunchKernelGGL((lat_sweep_kernel<PPL, DELAY>), dim3(2 * B), dim3(64), 0, s, logits, T, B, V, labels, label_offsets, \
-                       seq_len, max_label_len, win_lo, win_hi, delay_penalty, lse, alpha, beta, m.srow,                 \
-                       (grad || entry_sum) ? 1 : 0, loss, lp2, status)
-    switch (e.delay ? -m.ppl : m.ppl) {                  // the sign picks the DELAY instantiations
-    case 1: LC_LAT(1, false); break;
-    case 2: LC_LAT(2, false); break;
-    case 4: LC_LAT(4, false); break;
-    case 8: LC_LAT(8, false); break;
-    case 16: LC_LAT(16, false); break;
-    case 32: LC_LAT(32, false); break;
-    case -1: LC_LAT(1, true); break;
-    case -2: LC_LAT(2, true); break;
-    case -4: LC_LAT(4, true); break;
-    case -8: LC_LAT(8, true); break;
-    case -16: LC_LAT(16, true); break;
-    default: LC_LAT(32, true); break;
+#define LC_LAT(PPL, DELAY, ENT)                                                                                         \
+    hipLaunchKernelGGL((lat_sweep_kernel<PPL, DELAY, ENT>), dim3(2 * B), dim3(64), 0, s, logits, T, B, V, labels,       \
+                       label_offsets, seq_len, max_label_len, win_lo, win_hi, weight, lse, alpha, beta, m.srow,         \
+                       (grad || entry_sum) ? 1 : 0, loss, lp2, status, malpha, mbeta, ebar, entropy)
+    switch (e.delay ? -m.ppl : e.entropy ? 64 + m.ppl : m.ppl) {         // the sign picks the DELAY instantiations, + 64 ENT
+    case 1: LC_LAT(1, false, false); break;
+    case 2: LC_LAT(2, false, false); break;
+    case 4: LC_LAT(4, false, false); break;
+    case 8: LC_LAT(8, false, false); break;
+    case 16: LC_LAT(16, false, false); break;
+    case 32: LC_LAT(32, false, false); break;
+    case 65: LC_LAT(1, false, true); break;
+    case 66: LC_LAT(2, false, true); break;
+    case 68: LC_LAT(4, false, true); break;
+    case 72: LC_LAT(8, false, true); break;
+    case 80: LC_LAT(16, false, true); break;
+    case 96: LC_LAT(32, false, true); break;
+    case -1: LC_LAT(1, true, false); break;
+    case -2: LC_LAT(2, true, false); break;
+    case -4: LC_LAT(4, true, false); break;
+    case -8: LC_LAT(8, true, false); break;
+    case -16: LC_LAT(16, true, false); break;
+    default: LC_LAT(32, true, false); break;
     }
 #undef LC_LAT
     LC_CHECK_LAUNCH(e.sweep);
-    if (grad && entry_sum) {
-        hipLaunchKernelGGL(lat_grad_kernel<true>, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, label_offsets, seq_len,
-                           lse, alpha, beta, m.srow, lp2, status, order, m.pitch, first, cnt, grad, fterm);
+#define LC_LAT_GRAD(ENTRY, ENT)                                                                                         \
+    hipLaunchKernelGGL((lat_grad_kernel<ENTRY, ENT>), dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, label_offsets, \
+                       seq_len, lse, alpha, beta, m.srow, lp2, status, order, m.pitch, first, cnt, grad, fterm, malpha,  \
+                       mbeta, ebar, weight)
+    if (grad && entropy) {
+        LC_LAT_GRAD(false, true);
+        LC_CHECK_LAUNCH(e.grad);
+    } else if (grad && entry_sum) {
+        LC_LAT_GRAD(true, false);
         LC_CHECK_LAUNCH(e.grad);
     } else if (grad) {
-        hipLaunchKernelGGL(lat_grad_kernel<false>, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, label_offsets, seq_len,
-                           lse, alpha, beta, m.srow, lp2, status, order, m.pitch, first, cnt, grad, fterm);
+        LC_LAT_GRAD(false, false);
         LC_CHECK_LAUNCH(e.grad);
     } else if (entry_sum) {
         hipLaunchKernelGGL(lat_entry_kernel, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, labels, label_offsets,
                            seq_len, lse, alpha, beta, m.srow, lp2, status, fterm);
         LC_CHECK_LAUNCH(e.entry);
     }
+#undef LC_LAT_GRAD
     if (entry_sum) {
         hipLaunchKernelGGL(lat_fold_kernel, dim3(B), dim3(64), 0, s, fterm, T, seq_len, status, entry_sum);
         LC_CHECK_LAUNCH(e.fold);
@@ -521,12 +632,26 @@ int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, cons
 
 extern "C" size_t lc_ctc_window_workspace_bytes(int T, int B, int V, int max_label_len)
 {
-    return lat_workspace_bytes(T, B, V, max_label_len, false);
+    return lat_workspace_bytes(T, B, V, max_label_len, false, false);
 }
 
 extern "C" size_t lc_ctc_delay_workspace_bytes(int T, int B, int V, int max_label_len)
 {
-    return lat_workspace_bytes(T, B, V, max_label_len, true);
+    return lat_workspace_bytes(T, B, V, max_label_len, true, false);
+}
+
+extern "C" size_t lc_ctc_entropy_workspace_bytes(int T, int B, int V, int max_label_len)
+{
+    return lat_workspace_bytes(T, B, V, max_label_len, false, true);
+}
+
+extern "C" int lc_ctc_loss_entropy(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                                   const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
+                                   float entropy_weight, float *loss, float *entropy, float *grad, void *workspace,
+                                   size_t workspace_bytes, lc_stream_t stream)
+{
+    return lat_launch(LAT_ENTROPY, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi,
+                      entropy_weight, loss, entropy, grad, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lc_ctc_loss_windowed(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,

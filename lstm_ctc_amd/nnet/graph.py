@@ -223,6 +223,16 @@ class CTCGraph:
     ``entry_sum / entry_labels`` is the mean frame at which a label is entered; ``entry_sum_total`` / ``entry_labels_total``
     sum over the steps.  0 is plain CTC plus the metric.  ``None`` is the step without it, untouched.
 
+    ``entropy_weight=eta`` (new, ``objective="ctc"`` only; a finite float >= 0) is maximum-entropy CTC (Liu et al. 2018):
+    the criterion is ``loss - eta * H``, H the entropy in nats of the posterior over the utterance's feasible paths
+    (``ops.ctc_loss_entropy`` where the step calls ``ops.ctc_loss`` / ``ops.ctc_loss_windowed``; with ``align_window`` the
+    windows go to it and H is the entropy over the paths inside them).  ``eval_loss`` / ``loss`` are that criterion; the output
+    gains ``path_entropy`` (the float64 sum of H over the utterances with a finite, non-skipped loss) and
+    ``path_entropy_frames`` (the sum of their sequence lengths), so that ``path_entropy / path_entropy_frames`` is the entropy
+    in nats per utterance-frame; ``path_entropy_total`` / ``path_entropy_frames_total`` sum over the steps (each rank its
+    own).  0 is plain CTC plus the metric.  It does not combine with ``delay_penalty`` (the entropy of the tilted posterior
+    is not built).  ``None`` is the step without it, untouched.
+
     ``spec_augment=SpecAugment(...)`` (new, training graphs, every objective; ``nnet.augment``) masks the input of every
     TRAINING step on the device: the model reads ``ops.spec_augment(x, ...)``, written OUT OF PLACE - the caller's ``x`` is
     never changed, so ``step_device`` callers may pass the same tensor step after step.  The draws are seeded with the step's
@@ -253,7 +263,7 @@ class CTCGraph:
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None,
                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None,
-                 consistency_weight=None):
+                 consistency_weight=None, entropy_weight=None):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
@@ -281,6 +291,15 @@ class CTCGraph:
             delay_penalty = _checked_number("delay_penalty", delay_penalty, 0, False, "a finite float >= 0 or None")
         self.delay_penalty = delay_penalty
         self.entry_sum_total, self.entry_labels_total = 0.0, 0
+        if entropy_weight is not None:
+            if objective != "ctc":
+                raise ValueError("entropy_weight regularises the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
+            entropy_weight = _checked_number("entropy_weight", entropy_weight, 0, False, "a finite float >= 0 or None")
+            if delay_penalty is not None:
+                raise ValueError("entropy_weight does not combine with delay_penalty (the entropy of the tilted path "
+                                 "posterior is not built)")
+        self.entropy_weight = entropy_weight
+        self.path_entropy_total, self.path_entropy_frames_total = 0.0, 0
         self.spec_layout = None
         if spec_augment is not None:
             from . import augment
@@ -580,11 +599,15 @@ class CTCGraph:
     # host, reduced at the step's one copy; ``outputs(host, out, fetch_eval)`` writing size, eval_loss, eval and its own keys
     # into ``out`` from the fetched {name: float} - and adding to its ``*_total`` counters, so only for a step that completed.
     def _ctc_criterion(self, logits, b, train):
-        entry_b = None
+        entry_b = entropy_b = None
         if self.delay_penalty is not None:
             lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
             loss_b, entry_b, grad = ops.ctc_loss_delay(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.delay_penalty,
                                                        win_lo=lo_d, win_hi=hi_d, want_grad=train)
+        elif self.entropy_weight is not None:
+            lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
+            loss_b, entropy_b, grad = ops.ctc_loss_entropy(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.entropy_weight,
+                                                           win_lo=lo_d, win_hi=hi_d, want_grad=train)
         elif self.align_window is not None:
             loss_b, grad = ops.ctc_loss_windowed(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, b.windows[0], b.windows[1],
                                                  want_grad=train)
@@ -592,6 +615,10 @@ class CTCGraph:
             loss_b, grad = ops.ctc_loss(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, want_grad=train)
 
         def scalars():
+            if entropy_b is not None:                                            # the criterion: sum of loss - eta * H
+                return ([("eval_loss", (loss_b - self.entropy_weight * entropy_b).sum())]
+                        + list(zip(("path_entropy", "path_entropy_frames"),
+                                   self._entropy_scalars(loss_b, entropy_b, b.offs_d, b.seq_d))))
             pairs = [("eval_loss", loss_b.sum())]                                # graph.py:116 reduce_sum, in float32
             if entry_b is not None:
                 pairs += zip(("entry_sum", "entry_labels"), self._entry_scalars(loss_b, entry_b, b.offs_d, b.seq_d))
@@ -603,6 +630,10 @@ class CTCGraph:
                 out["entry_sum"], out["entry_labels"] = host["entry_sum"], int(host["entry_labels"])
                 self.entry_sum_total += out["entry_sum"]
                 self.entry_labels_total += out["entry_labels"]
+            if entropy_b is not None:
+                out["path_entropy"], out["path_entropy_frames"] = host["path_entropy"], int(host["path_entropy_frames"])
+                self.path_entropy_total += out["path_entropy"]
+                self.path_entropy_frames_total += out["path_entropy_frames"]
         return grad, scalars, outputs
 
     def _xent_criterion(self, logits, b, train):
@@ -642,6 +673,15 @@ class CTCGraph:
         ok = torch.isfinite(loss_b) & (seq_d > 0) & (n <= seq_d)
         zero = torch.zeros((), dtype=torch.float64, device=loss_b.device)
         return [torch.where(ok, entry_b.to(torch.float64), zero).sum(), torch.where(ok, n, torch.zeros_like(n)).sum()]
+
+    @staticmethod
+    def _entropy_scalars(loss_b, entropy_b, offs_d, seq_d):
+        """entropy_weight: [sum of entropy, sum of seq_len] over the utterances with a finite, non-skipped loss."""
+        n = (offs_d[1:] - offs_d[:-1]).to(torch.int64)
+        ok = torch.isfinite(loss_b) & (seq_d > 0) & (n <= seq_d)
+        zero = torch.zeros((), dtype=torch.float64, device=loss_b.device)
+        frames = seq_d.to(torch.int64)
+        return [torch.where(ok, entropy_b.to(torch.float64), zero).sum(), torch.where(ok, frames, torch.zeros_like(frames)).sum()]
 
     def _kd_outputs(self, out, host):
         """Writes kd_loss / kd_frames / kd_agree into ``out`` and returns what the term adds to ``loss``."""
@@ -848,19 +888,21 @@ def load_params(ps, path):
 
 # ----------------------------------------------------------------------------------------------------- reference-named factories
 def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None, align_window=None,
-                                    teacher_weight=None, teacher_temperature=1.0, delay_penalty=None):
+                                    teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, entropy_weight=None):
     return CTCGraph(pipeline, nnet_config, device=device, seed=seed, align_window=align_window,
-                    teacher_weight=teacher_weight, teacher_temperature=teacher_temperature, delay_penalty=delay_penalty)
+                    teacher_weight=teacher_weight, teacher_temperature=teacher_temperature, delay_penalty=delay_penalty,
+                    entropy_weight=entropy_weight)
 
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None,
                                   teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None,
-                                  consistency_weight=None):
+                                  consistency_weight=None, entropy_weight=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
                     align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature,
-                    delay_penalty=delay_penalty, spec_augment=spec_augment, consistency_weight=consistency_weight)
+                    delay_penalty=delay_penalty, spec_augment=spec_augment, consistency_weight=consistency_weight,
+                    entropy_weight=entropy_weight)
 
 
 def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None, teacher_weight=None,

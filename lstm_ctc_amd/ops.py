@@ -337,6 +337,44 @@ def ctc_loss_delay(logits, labels, offsets, seq_len, max_label_len, delay_penalt
     return loss, entry, grad
 
 
+def ctc_loss_entropy(logits, labels, offsets, seq_len, max_label_len, entropy_weight, win_lo=None, win_hi=None, want_grad=True):
+    """Maximum-entropy CTC (Liu et al. 2018) - no reference counterpart.  Arguments as for :func:`ctc_loss`, plus
+    entropy_weight (eta, any finite float) and, optionally, the windows of :func:`ctc_loss_windowed` (both or none).
+    Returns (loss[B], entropy[B], grad[T,B,V] or None): loss is plain (windowed) CTC's, entropy the entropy in nats of the
+    posterior over the feasible paths, grad the exact gradient of ``loss - entropy_weight * entropy``."""
+    lib = _lib.load()
+    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
+    if isinstance(entropy_weight, bool) or not np.isfinite(entropy_weight):
+        raise ValueError("ctc_loss_entropy: entropy_weight must be a finite float, got %r" % (entropy_weight,))
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError("ctc_loss_entropy: win_lo and win_hi go together (both or none)")
+    if win_lo is not None:
+        assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
+        if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
+            raise ValueError("ctc_loss_entropy: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
+                             % (win_lo.numel(), win_hi.numel(), labels.numel()))
+        win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    entropy = torch.empty(B, dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits) if want_grad else None
+    nbytes = lib.lc_ctc_entropy_workspace_bytes(T, B, V, int(max_label_len))
+    ws = workspace("ctc_entropy", nbytes, logits.device)
+    if labels.numel() == 0:
+        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
+        if win_lo is not None:
+            win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
+            win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    ev = _prof_begin()
+    _lib.check(lib.lc_ctc_loss_entropy(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len),
+                                       _ptr(win_lo), _ptr(win_hi), float(entropy_weight), _ptr(loss), _ptr(entropy),
+                                       _ptr(grad), _ptr(ws), nbytes, _stream()), "lc_ctc_loss_entropy")
+    _prof_end("ctc", (T, B, V), ev)
+    return loss, entropy, grad
+
+
 WINDOW_OPEN = np.iinfo(np.int32).max
 
 
