@@ -1404,6 +1404,119 @@ extern "C" size_t lc_gemm_workspace_bytes(int M, int N, int K)
     return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
 }
 
+// ---- the rules every product shares --------------------------------------------------------------------------------------
+// The K split of one product: `want` slices (pick_splitk / pick_splitk_big) hold only with a slab to put them in - an active
+// fused epilogue lives in the product kernel, so it means no split, and so does a missing or too small workspace.  The chunk is
+// rounded up to whole k tiles of `bk`, and the slice count follows from the chunk.
+struct KSplit {
+    int nsl, kchunk;
+    float *slab;
+    size_t slab_slice;
+};
+static KSplit plan_ksplit(int want, int M, int N, int K, int bk, const EpiArgs &epi, void *workspace, size_t workspace_bytes)
+{
+    if (want > 1 && (epi_active(epi) || !workspace || workspace_bytes < (size_t)want * M * N * sizeof(float))) want = 1;
+    if (want <= 1) return {1, K > 0 ? K : 1, nullptr, (size_t)M * N};
+    const int kchunk = lc_cdiv(lc_cdiv(K, want), bk) * bk, nsl = lc_cdiv(K, kchunk);
+    return {nsl, kchunk, nsl > 1 ? (float *)workspace : nullptr, (size_t)M * N};
+}
+static KSplit unsplit(int K) { return {1, K, nullptr, 0}; }      // the strips beside a 256 x 256 interior
+static void set_ksplit(GemmArgs &g, const KSplit &ks)           // (on the WHOLE problem: the slab's pitch is its N)
+{
+    g.kchunk = ks.kchunk; g.slab = ks.slab; g.slab_slice = ks.slab_slice; g.slab_ld = g.N;
+}
+// C = alpha * sum of the slices + beta C + bias behind a split product (nothing to do for an unsplit one)
+static int splitk_reduce(const KSplit &ks, int M, int N, float alpha, float beta, float *C, int ldc, const float *bias,
+                         hipStream_t s)
+{
+    if (ks.nsl <= 1) return LC_OK;
+    const size_t quads = (size_t)M * N / 4;
+    int g = (int)((quads + 255) / 256);
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, s, ks.slab, ks.nsl, M, N, alpha, beta, C, ldc, bias);
+    LC_CHECK_LAUNCH("splitk_reduce");
+    return LC_OK;
+}
+// One workgroup per CU on the 256 x 256 kernels: the last round of 256 must be nearly full (32000 x 1280 = 625 tiles fill 2.44
+// rounds and run 11 % slower there than on the 128 x 128 kernel's 768 slots) - whole rounds to 90 %, and half a chip at least.
+static bool fills_whole_rounds(long long wgs)
+{
+    const long long rounds = (wgs + 255) / 256;
+    return wgs >= 128 && wgs * 10 >= rounds * 256 * 9;
+}
+
+// The argument block of the whole product; the K split comes from set_ksplit.
+static GemmArgs gemm_args(const EpiArgs &epi, int M, int N, int K, float alpha, float beta, const float *A, int lda,
+                          const float *B, int ldb, float *C, int ldc, const float *bias)
+{
+    GemmArgs p;
+    p.epi = epi;
+    p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta;
+    p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias;
+    p.vecA = aligned16(A) && (lda % 4 == 0);
+    p.vecB = aligned16(B) && (ldb % 4 == 0);
+    p.A2 = p.B2 = nullptr; p.k1 = 0;
+    return p;
+}
+// ... with bf16 operands, k contiguous or K-major (their alignment is the entries' precondition: vecA = vecB = 1)
+static SGemmArgs sgemm_args(const EpiArgs &epi, int M, int N, int K, float alpha, float beta, const uint16_t *A, int lda,
+                            const uint16_t *B, int ldb, float *C, int ldc, const float *bias)
+{
+    SGemmArgs sp;
+    sp.g = gemm_args(epi, M, N, K, alpha, beta, nullptr, lda, nullptr, ldb, C, ldc, bias);
+    sp.A = A; sp.B = B;
+    sp.A2 = sp.B2 = nullptr; sp.k1 = 0;
+    return sp;
+}
+
+// The ragged edges of a product `p` whose interior of whole tiles, rows [0, Mi) x columns [0, Ni), went to a kernel without
+// bounds checks: the right strip is all M rows of columns [Ni, N), the bottom strip rows [Mi, M) of columns [0, Ni).  Each moves
+// the origin of its operand, of C, of bias, of the epilogue's block and of the slab (when the strips share the interior's split).
+static void strip_columns(GemmArgs &g, int Ni)
+{
+    if (g.slab) g.slab += Ni;
+    g.N -= Ni;
+    g.C += Ni;
+    g.epi = epi_block(g.epi, 0, Ni);
+    if (g.bias) g.bias += Ni;
+}
+static void strip_rows(GemmArgs &g, int Mi, int Ni)
+{
+    if (g.slab) g.slab += (size_t)Mi * g.N;
+    g.M -= Mi; g.N = Ni;
+    g.C += (size_t)Mi * g.ldc;
+    g.epi = epi_block(g.epi, Mi, 0);
+}
+static GemmArgs right_strip(GemmArgs p, int tb, int Ni)              // float operands, op(A) / op(B) as (ta, tb) say
+{
+    p.B = tb ? p.B + (size_t)Ni * p.ldb : p.B + Ni;
+    if (p.B2) p.B2 += (size_t)Ni * p.ldb;                             // (a second pair is NT)
+    p.vecB = aligned16(p.B) && (p.ldb % 4 == 0);
+    strip_columns(p, Ni);
+    return p;
+}
+static GemmArgs bottom_strip(GemmArgs p, int ta, int Mi, int Ni)
+{
+    p.A = ta ? p.A + Mi : p.A + (size_t)Mi * p.lda;
+    if (p.A2) p.A2 += (size_t)Mi * p.lda;
+    p.vecA = aligned16(p.A) && (p.lda % 4 == 0);
+    strip_rows(p, Mi, Ni);
+    return p;
+}
+static SGemmArgs right_strip(SGemmArgs p, int Ni)                     // bf16 operands, NT
+{
+    p.B += (size_t)Ni * p.g.ldb;
+    strip_columns(p.g, Ni);
+    return p;
+}
+static SGemmArgs bottom_strip(SGemmArgs p, int Mi, int Ni)
+{
+    p.A += (size_t)Mi * p.g.lda;
+    strip_rows(p.g, Mi, Ni);
+    return p;
+}
+
+// ---- one launch function per kernel family -------------------------------------------------------------------------------
 // One kernel launch over the sub-problem whose origin is (A, B, C, bias, slab) as given.
 static void gemm_launch_part(bool bf16, bool fast, int ta, int tb, GemmArgs p, int nsl, hipStream_t s)
 {
@@ -1425,6 +1538,16 @@ static void gemm_launch_part(bool bf16, bool fast, int ta, int tb, GemmArgs p, i
     else LC_GEMM(true, true);
 #undef LC_GEMM
 }
+// gemm_f32g_kernel over `tiles` whole 256 x 256 tiles and nsl K slices; a second operand pair (NT only) makes it the SEG2 form
+static void launch_f32g(int ta, int tb, long long tiles, int nsl, hipStream_t s, const GemmArgs &q)
+{
+    const dim3 grid((unsigned)tiles, 1, (unsigned)nsl), block(GNT);
+    if (ta && !tb) hipLaunchKernelGGL((gemm_f32g_kernel<true, true>), grid, block, 0, s, q);
+    else if (ta) hipLaunchKernelGGL((gemm_f32g_kernel<true, false>), grid, block, 0, s, q);
+    else if (!tb) hipLaunchKernelGGL((gemm_f32g_kernel<false, true>), grid, block, 0, s, q);
+    else if (!q.A2) hipLaunchKernelGGL((gemm_f32g_kernel<false, false>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((gemm_f32g_kernel<false, false, true>), grid, block, 0, s, q);
+}
 
 static int gemm_launch(bool bf16, const char *who, int ta, int tb, int M, int N, int K, float alpha, const float *A,
                        int lda, const float *B, int ldb, float beta, float *C, int ldc, const float *bias,
@@ -1437,14 +1560,7 @@ static int gemm_launch(bool bf16, const char *who, int ta, int tb, int M, int N,
     LC_CHECK_ARG(lda >= (ta ? M : K) && ldb >= (tb ? K : N) && ldc >= N, "%s: leading dimension too small", who);
     hipStream_t s = (hipStream_t)stream;
     const int bk = bf16 ? HBK : BK;
-    if (epi_active(epi)) { workspace = nullptr; workspace_bytes = 0; }      // a fused epilogue lives in the product kernel: no K split
-    GemmArgs p;
-    p.epi = epi;
-    p.A2 = p.B2 = nullptr; p.k1 = 0;
-    p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta;
-    p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias;
-    p.vecA = aligned16(A) && (lda % 4 == 0);
-    p.vecB = aligned16(B) && (ldb % 4 == 0);
+    GemmArgs p = gemm_args(epi, M, N, K, alpha, beta, A, lda, B, ldb, C, ldc, bias);
     LC_CHECK_ARG((long long)lc_cdiv(M, BM) * lc_cdiv(N, BN) < (1ll << 31), "%s: grid too large", who);
     // whole 256 x 256 tiles, 32-deep K chunks, enough of them for half the chip: the LDS-DMA kernel
     // (LC_GEMM_F32_BIG: 0 = never, 2 = whenever the shape is eligible - the tests use it on small shapes -, default: when
@@ -1457,69 +1573,30 @@ static int gemm_launch(bool bf16, const char *who, int ta, int tb, int M, int N,
         int Mi = M / GBM * GBM;
         const int Ni = N / GBN * GBN;
         const bool exact = Mi == M && Ni == N;
-        int nb = exact ? pick_splitk_big(M, N, K, FGBK) : 1;
-        if (nb > 1 && (!workspace || workspace_bytes < (size_t)nb * M * N * sizeof(float))) nb = 1;
-        if (nb <= 1) Mi = gemm_whole_round_row_tiles(Mi / GBM, Ni / GBN) * GBM;      // whole rounds; the rest as a bottom strip
+        const KSplit ks = plan_ksplit(exact ? pick_splitk_big(M, N, K, FGBK) : 1, M, N, K, FGBK, epi, workspace, workspace_bytes);
+        if (ks.nsl <= 1) Mi = gemm_whole_round_row_tiles(Mi / GBM, Ni / GBN) * GBM;      // whole rounds; the rest as a bottom strip
         const long long tiles = (long long)(Mi / GBM) * (Ni / GBN);
         const long long spanA = ta ? (long long)K * lda * 4 + 4ll * GBM : (long long)(GBM - 1) * lda * 4 + 4ll * K;
         const long long spanB = tb ? (long long)(GBN - 1) * ldb * 4 + 4ll * K : (long long)K * ldb * 4 + 4ll * GBN;
-        // one workgroup per CU: the last round of 256 must be nearly full (32000 x 1280 = 625 tiles fill 2.44 rounds and run
-        // 11 % slower here than on the 128 x 128 kernel's 768 slots)
-        const long long wgs = tiles * (nb > 1 ? nb : 1), rounds = (wgs + 255) / 256;
-        const bool fills = wgs >= 128 && wgs * 10 >= rounds * 256 * 9;
-        if (tiles > 0 && (fills || big_mode == 2) && spanA < 0x7fffffffll && spanB < 0x7fffffffll) {
+        if (tiles > 0 && (fills_whole_rounds(tiles * ks.nsl) || big_mode == 2) && spanA < 0x7fffffffll && spanB < 0x7fffffffll) {
             GemmArgs q = p;
+            set_ksplit(q, ks);
             q.M = Mi; q.N = Ni;
-            q.kchunk = nb > 1 ? lc_cdiv(lc_cdiv(K, nb), FGBK) * FGBK : K;
-            if (nb > 1) nb = lc_cdiv(K, q.kchunk);
-            q.slab = nb > 1 ? (float *)workspace : nullptr;
-            q.slab_slice = (size_t)M * N;
-            q.slab_ld = N;
-            const dim3 grid((unsigned)tiles, 1, (unsigned)(nb > 1 ? nb : 1)), block(GNT);
-            if (ta && !tb) hipLaunchKernelGGL((gemm_f32g_kernel<true, true>), grid, block, 0, s, q);
-            else if (ta) hipLaunchKernelGGL((gemm_f32g_kernel<true, false>), grid, block, 0, s, q);
-            else if (!tb) hipLaunchKernelGGL((gemm_f32g_kernel<false, true>), grid, block, 0, s, q);
-            else hipLaunchKernelGGL((gemm_f32g_kernel<false, false>), grid, block, 0, s, q);
-            p.kchunk = K > 0 ? K : 1; p.slab = nullptr; p.slab_slice = 0; p.slab_ld = N;      // the strips: unsplit
-            if (Ni < N) {                               // right strip: all M rows, columns [Ni, N)
-                q = p;
-                q.N = N - Ni;
-                q.B = tb ? B + (size_t)Ni * ldb : B + Ni;
-                q.C = C + Ni;
-                q.epi = epi_block(p.epi, 0, Ni);
-                q.bias = bias ? bias + Ni : nullptr;
-                q.vecB = aligned16(q.B) && (ldb % 4 == 0);
-                gemm_launch_part(false, false, ta, tb, q, 1, s);
-            }
-            if (Mi < M) {                               // bottom strip: rows [Mi, M), columns [0, Ni)
-                q = p;
-                q.M = M - Mi; q.N = Ni;
-                q.A = ta ? A + Mi : A + (size_t)Mi * lda;
-                q.C = C + (size_t)Mi * ldc;
-                q.epi = epi_block(p.epi, Mi, 0);
-                q.vecA = aligned16(q.A) && (lda % 4 == 0);
+            launch_f32g(ta, tb, tiles, ks.nsl, s, q);
+            set_ksplit(p, unsplit(K));                  // the strips: on the 128 x 128 kernel
+            if (Ni < N) gemm_launch_part(false, false, ta, tb, right_strip(p, tb, Ni), 1, s);
+            if (Mi < M) {
+                q = bottom_strip(p, ta, Mi, Ni);
                 // (a tail of whole 128 x 128 tiles - the rows cut off for whole rounds - takes the kernel without bounds checks)
                 const bool fast = q.M % BM == 0 && q.N % BN == 0 && K % BK == 0 && q.vecA && q.vecB;
                 gemm_launch_part(false, fast, ta, tb, q, 1, s);
             }
             LC_CHECK_LAUNCH(who);
-            if (nb > 1) {
-                const size_t quads = (size_t)M * N / 4;
-                int g = (int)((quads + 255) / 256);
-                if (g > 2048) g = 2048;
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, s, (float *)workspace, nb, M, N, alpha, beta, C, ldc, bias);
-                LC_CHECK_LAUNCH("splitk_reduce");
-            }
-            return LC_OK;
+            return splitk_reduce(ks, M, N, alpha, beta, C, ldc, bias, s);
         }
     }
-    int nsl = pick_splitk(M, N, K);
-    if (nsl > 1 && (!workspace || workspace_bytes < (size_t)nsl * M * N * sizeof(float))) nsl = 1;   // no slab: unsplit
-    p.kchunk = nsl > 1 ? lc_cdiv(lc_cdiv(K, nsl), bk) * bk : (K > 0 ? K : 1);
-    if (nsl > 1) nsl = lc_cdiv(K, p.kchunk);
-    p.slab = nsl > 1 ? (float *)workspace : nullptr;
-    p.slab_slice = (size_t)M * N;
-    p.slab_ld = N;
+    const KSplit ks = plan_ksplit(pick_splitk(M, N, K), M, N, K, bk, epi, workspace, workspace_bytes);
+    set_ksplit(p, ks);
     // The no-bounds-check kernel needs whole 128x128 tiles; a ragged M or N edge (the MoE head's N = E*V, a last
     // partial batch) is peeled off into one or two strips for the generic kernel instead of demoting the whole
     // product to it.
@@ -1528,44 +1605,18 @@ static int gemm_launch(bool bf16, const char *who, int ta, int tb, int M, int N,
     // Peeling only pays when the interior launch fills the chip on its own: three back-to-back launches of a handful of
     // workgroups each (a 320 x 320 weight gradient: 128 + 96 + 64) took 359 us where one generic launch takes ~120.
     const bool ragged = Mi < M || Ni < N;
-    const long long interior_wgs = (long long)(Mi / BM) * (Ni / BN) * (nsl > 1 ? nsl : 1);
+    const long long interior_wgs = (long long)(Mi / BM) * (Ni / BN) * ks.nsl;
     if (kfast && Mi > 0 && Ni > 0 && !(ragged && interior_wgs < 256)) {
         GemmArgs q = p;
         q.M = Mi; q.N = Ni;
-        gemm_launch_part(bf16, true, ta, tb, q, nsl, s);
-        if (Ni < N) {                                   // right strip: all M rows, columns [Ni, N)
-            q = p;
-            q.N = N - Ni;
-            q.B = tb ? B + (size_t)Ni * ldb : B + Ni;
-            q.C = C + Ni;
-            q.epi = epi_block(p.epi, 0, Ni);
-            q.bias = bias ? bias + Ni : nullptr;
-            q.vecB = aligned16(q.B) && (ldb % 4 == 0);
-            if (q.slab) q.slab += Ni;
-            gemm_launch_part(bf16, false, ta, tb, q, nsl, s);
-        }
-        if (Mi < M) {                                   // bottom strip: rows [Mi, M), columns [0, Ni)
-            q = p;
-            q.M = M - Mi; q.N = Ni;
-            q.A = ta ? A + Mi : A + (size_t)Mi * lda;
-            q.C = C + (size_t)Mi * ldc;
-            q.epi = epi_block(p.epi, Mi, 0);
-            q.vecA = aligned16(q.A) && (lda % 4 == 0);
-            if (q.slab) q.slab += (size_t)Mi * N;
-            gemm_launch_part(bf16, false, ta, tb, q, nsl, s);
-        }
+        gemm_launch_part(bf16, true, ta, tb, q, ks.nsl, s);
+        if (Ni < N) gemm_launch_part(bf16, false, ta, tb, right_strip(p, tb, Ni), ks.nsl, s);
+        if (Mi < M) gemm_launch_part(bf16, false, ta, tb, bottom_strip(p, ta, Mi, Ni), ks.nsl, s);
     } else {
-        gemm_launch_part(bf16, false, ta, tb, p, nsl, s);
+        gemm_launch_part(bf16, false, ta, tb, p, ks.nsl, s);
     }
     LC_CHECK_LAUNCH(who);
-    if (nsl > 1) {
-        const size_t quads = (size_t)M * N / 4;
-        int g = (int)((quads + 255) / 256);
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, s, p.slab, nsl, M, N, alpha, beta, C, ldc, bias);
-        LC_CHECK_LAUNCH("splitk_reduce");
-    }
-    return LC_OK;
+    return splitk_reduce(ks, M, N, alpha, beta, C, ldc, bias, s);
 }
 
 extern "C" int lc_gemm_f32(int ta, int tb, int M, int N, int K, float alpha, const float *A, int lda,
@@ -1591,42 +1642,32 @@ extern "C" int lc_gemm_f32_nt2(int M, int N, int K1, int K2, float alpha, const 
     if (M == 0 || N == 0) return LC_OK;
     LC_CHECK_ARG(lda >= std::max(K1, K2) && ldb >= std::max(K1, K2) && ldc >= N, "%s: leading dimension too small", who);
     hipStream_t s = (hipStream_t)stream;
-    auto sequence = [&](int m, int n, const float *a1, const float *a2, const float *b1, const float *b2, float *c,
-                        const float *bi, const EpiArgs &e) -> int {
-        int rc = gemm_launch(false, who, 0, 1, m, n, K1, alpha, a1, lda, b1, ldb, beta, c, ldc, bi, nullptr, 0, stream);
+    auto sequence = [&](const GemmArgs &r) -> int {
+        int rc = gemm_launch(false, who, 0, 1, r.M, r.N, K1, alpha, r.A, lda, r.B, ldb, beta, r.C, ldc, r.bias, nullptr, 0, stream);
         if (rc != LC_OK) return rc;
-        g_epi_next = e;                          // (taken by the call below)
-        return gemm_launch(false, who, 0, 1, m, n, K2, alpha, a2, lda, b2, ldb, 1.f, c, ldc, nullptr, nullptr, 0, stream);
+        g_epi_next = r.epi;                      // (taken by the call below)
+        return gemm_launch(false, who, 0, 1, r.M, r.N, K2, alpha, r.A2, lda, r.B2, ldb, 1.f, r.C, ldc, nullptr, nullptr, 0, stream);
     };
+    GemmArgs p = gemm_args(epi, M, N, K1 + K2, alpha, beta, A1, lda, B1, ldb, C, ldc, bias);
+    p.A2 = A2; p.B2 = B2; p.k1 = K1;
+    set_ksplit(p, unsplit(K1 + K2));
     const int Mi = M / GBM * GBM, Ni = N / GBN * GBN;
-    const long long tiles = (long long)(Mi / GBM) * (Ni / GBN), rounds = (tiles + 255) / 256;
+    const long long tiles = (long long)(Mi / GBM) * (Ni / GBN);
     const int big_mode = (int)lc_option(LC_OPT_GEMM_F32_BIG, 1);
-    const bool vec = aligned16(A1) && aligned16(A2) && aligned16(B1) && aligned16(B2) && lda % 4 == 0 && ldb % 4 == 0;
-    const bool fills = tiles >= 128 && tiles * 10 >= rounds * 256 * 9;
+    const bool vec = p.vecA && p.vecB && aligned16(A2) && aligned16(B2);
     const long long span = (long long)(GBM - 1) * std::max(lda, ldb) * 4 + 4ll * std::max(K1, K2);
-    if (!(big_mode != 0 && vec && tiles > 0 && (fills || big_mode == 2) && K1 % FGBK == 0 && K2 % FGBK == 0 &&
+    if (!(big_mode != 0 && vec && tiles > 0 && (fills_whole_rounds(tiles) || big_mode == 2) && K1 % FGBK == 0 && K2 % FGBK == 0 &&
           span < 0x7fffffffll))
-        return sequence(M, N, A1, A2, B1, B2, C, bias, epi);
-    GemmArgs q;
-    q.epi = epi;
-    q.M = Mi; q.N = Ni; q.K = K1 + K2; q.alpha = alpha; q.beta = beta;
-    q.A = A1; q.lda = lda; q.B = B1; q.ldb = ldb; q.C = C; q.ldc = ldc; q.bias = bias;
-    q.vecA = q.vecB = 1;
-    q.kchunk = K1 + K2; q.slab = nullptr; q.slab_slice = 0; q.slab_ld = N;
-    q.A2 = A2; q.B2 = B2; q.k1 = K1;
-    hipLaunchKernelGGL((gemm_f32g_kernel<false, false, true>), dim3((unsigned)tiles, 1, 1), dim3(GNT), 0, s, q);
+        return sequence(p);
+    GemmArgs q = p;
+    q.M = Mi; q.N = Ni;
+    launch_f32g(0, 1, tiles, 1, s, q);
     LC_CHECK_LAUNCH(who);
-    if (Ni < N) {                                   // right strip: all M rows, columns [Ni, N)
-        const int rc = sequence(M, N - Ni, A1, A2, B1 + (size_t)Ni * ldb, B2 + (size_t)Ni * ldb, C + Ni,
-                                bias ? bias + Ni : nullptr, epi_block(epi, 0, Ni));
+    if (Ni < N) {
+        const int rc = sequence(right_strip(p, 1, Ni));
         if (rc != LC_OK) return rc;
     }
-    if (Mi < M) {                                   // bottom strip: rows [Mi, M), columns [0, Ni)
-        const int rc = sequence(M - Mi, Ni, A1 + (size_t)Mi * lda, A2 + (size_t)Mi * lda, B1, B2, C + (size_t)Mi * ldc, bias,
-                                epi_block(epi, Mi, 0));
-        if (rc != LC_OK) return rc;
-    }
-    return LC_OK;
+    return Mi < M ? sequence(bottom_strip(p, 0, Mi, Ni)) : LC_OK;
 }
 extern "C" int lc_gemm_bf16(int ta, int tb, int M, int N, int K, float alpha, const float *A, int lda,
                             const float *B, int ldb, float beta, float *C, int ldc, const float *bias,
@@ -1658,6 +1699,10 @@ extern "C" int lc_cast_bf16(const float *x, int rows, int C, int ldx, uint16_t *
     return LC_OK;
 }
 
+// gemm_bf16s_kernel (128 x 128 tiles): FAST is the form without bounds checks.  (Defined behind gemm_bf16_nt_impl: a code object
+// lists its kernels in the order of their first use, and the 256 x 256 NT forms come first.)
+static void launch_bf16s(bool fast, int nsl, hipStream_t s, const SGemmArgs &q);
+
 // A2 / B2 / K2: optional second operand pair whose product is accumulated into the same C (lc_gemm_bf16_nt2); the epilogue
 // `epi` has been taken by the caller.
 static int gemm_bf16_nt_impl(const EpiArgs &epi, int M, int N, int K, float alpha, const uint16_t *A, int lda, const uint16_t *B,
@@ -1665,7 +1710,6 @@ static int gemm_bf16_nt_impl(const EpiArgs &epi, int M, int N, int K, float alph
                              size_t workspace_bytes, lc_stream_t stream, const uint16_t *A2 = nullptr,
                              const uint16_t *B2 = nullptr, int K2 = 0)
 {
-    if (epi_active(epi)) { workspace = nullptr; workspace_bytes = 0; }      // fused epilogue: no K split
     LC_CHECK_ARG(A && B && C, "lc_gemm_bf16_nt: null pointer");
     LC_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "lc_gemm_bf16_nt: negative dimension");
     if (M == 0 || N == 0) return LC_OK;
@@ -1673,18 +1717,11 @@ static int gemm_bf16_nt_impl(const EpiArgs &epi, int M, int N, int K, float alph
     LC_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && aligned16(A) && aligned16(B),
                  "lc_gemm_bf16_nt: K, lda, ldb must be multiples of 8 and the operands 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    SGemmArgs sp;
-    GemmArgs &p = sp.g;
-    p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta;
-    p.A = nullptr; p.lda = lda; p.B = nullptr; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias;
-    p.vecA = p.vecB = 1;
-    p.epi = epi;
-    sp.A = A; sp.B = B;
+    SGemmArgs sp = sgemm_args(epi, M, N, K, alpha, beta, A, lda, B, ldb, C, ldc, bias);
     LC_CHECK_ARG((long long)lc_cdiv(M, BM) * lc_cdiv(N, BN) < (1ll << 31), "lc_gemm_bf16_nt: grid too large");
     // whole 256 x 256 tiles and 64-deep K chunks: the LDS-DMA kernel, one workgroup per CU; ragged right / bottom edges (T * B
     // is a multiple of 256 only for every fourth T at B = 64) go to the 128 x 128 kernel as strips; K is split only for
     // exact shapes (the tall-K weight gradients)
-    sp.A2 = sp.B2 = nullptr; sp.k1 = 0;
     const bool big_off = lc_option(LC_OPT_GEMM_BF16_BIG, 1) == 0;
     int Mb = M / GBM * GBM;
     const int Nb = N / GBN * GBN;
@@ -1703,120 +1740,64 @@ static int gemm_bf16_nt_impl(const EpiArgs &epi, int M, int N, int K, float alph
     }
     if (big_ok) {
         const long long tiles = (long long)(Mb / GBM) * (Nb / GBN);
-        int nsl = (Mb == M && Nb == N && !seg2) ? pick_splitk_big(M, N, K) : 1;      // tall-K weight gradients: fill whole rounds of 256 CUs
-        if (nsl > 1 && (!workspace || workspace_bytes < (size_t)nsl * M * N * sizeof(float))) nsl = 1;
+        // tall-K weight gradients: fill whole rounds of 256 CUs
+        const KSplit ks = plan_ksplit((Mb == M && Nb == N && !seg2) ? pick_splitk_big(M, N, K) : 1, M, N, K, GBK, epi, workspace,
+                                      workspace_bytes);
         SGemmArgs q = sp;
+        set_ksplit(q.g, ks);
         q.g.M = Mb; q.g.N = Nb;
-        q.g.kchunk = nsl > 1 ? lc_cdiv(lc_cdiv(K, nsl), GBK) * GBK : K;
-        if (nsl > 1) nsl = lc_cdiv(K, q.g.kchunk);
-        q.g.slab = nsl > 1 ? (float *)workspace : nullptr;
-        q.g.slab_slice = (size_t)M * N;
-        q.g.slab_ld = N;
+        const dim3 grid((unsigned)tiles, 1, (unsigned)ks.nsl), block(GNT);
         if (seg2) {
             q.A2 = A2; q.B2 = B2; q.k1 = K;
             q.g.K = K + K2; q.g.kchunk = K + K2;
-            hipLaunchKernelGGL((gemm_bf16g_kernel<false, false, false, true>), dim3((unsigned)tiles, 1, 1), dim3(GNT), 0, s, q);
-        } else if (bf16g_persist_ok(tiles, nsl, K))
-            hipLaunchKernelGGL((gemm_bf16g_kernel<false, false, true>), dim3((unsigned)lc_num_cus(), 1, 1), dim3(GNT), 0, s, q);
+            hipLaunchKernelGGL((gemm_bf16g_kernel<false, false, false, true>), grid, block, 0, s, q);
+        } else if (bf16g_persist_ok(tiles, ks.nsl, K))
+            hipLaunchKernelGGL((gemm_bf16g_kernel<false, false, true>), dim3((unsigned)lc_num_cus(), 1, 1), block, 0, s, q);
         else
-            hipLaunchKernelGGL((gemm_bf16g_kernel<false, false>), dim3((unsigned)tiles, 1, (unsigned)(nsl > 1 ? nsl : 1)), dim3(GNT), 0, s, q);
-        p.kchunk = K; p.slab = nullptr; p.slab_slice = 0; p.slab_ld = N;       // the strips: unsplit, bounds-checked kernel
+            hipLaunchKernelGGL((gemm_bf16g_kernel<false, false>), grid, block, 0, s, q);
+        set_ksplit(sp.g, unsplit(K));                 // the strips: unsplit, bounds-checked kernel
         auto strip = [&](const SGemmArgs &r0) {
-            const long long nwg = (long long)lc_cdiv(r0.g.M, BM) * lc_cdiv(r0.g.N, BN);
             if (!seg2) {
                 // (a tail of whole 128 x 128 tiles - the rows cut off for whole rounds - takes the kernel without bounds checks)
-                if (r0.g.M % BM == 0 && r0.g.N % BN == 0 && K % SBK == 0)
-                    hipLaunchKernelGGL((gemm_bf16s_kernel<true>), dim3((unsigned)nwg, 1, 1), dim3(NT), 0, s, r0);
-                else
-                    hipLaunchKernelGGL((gemm_bf16s_kernel<false>), dim3((unsigned)nwg, 1, 1), dim3(NT), 0, s, r0);
+                launch_bf16s(r0.g.M % BM == 0 && r0.g.N % BN == 0 && K % SBK == 0, 1, s, r0);
                 return;
             }
             // two operand pairs on a strip: the first product (beta, bias, no epilogue), then the second accumulating into it
             SGemmArgs r = r0;
-            const EpiArgs e = r.g.epi;
             r.g.epi = EPI_NONE;
-            hipLaunchKernelGGL((gemm_bf16s_kernel<false>), dim3((unsigned)nwg, 1, 1), dim3(NT), 0, s, r);
+            launch_bf16s(false, 1, s, r);
             r.A = A2 + (r0.A - A); r.B = B2 + (r0.B - B);
-            r.g.K = K2; r.g.kchunk = K2; r.g.beta = 1.f; r.g.bias = nullptr; r.g.epi = e;
-            hipLaunchKernelGGL((gemm_bf16s_kernel<false>), dim3((unsigned)nwg, 1, 1), dim3(NT), 0, s, r);
+            r.g.K = K2; r.g.kchunk = K2; r.g.beta = 1.f; r.g.bias = nullptr; r.g.epi = r0.g.epi;
+            launch_bf16s(false, 1, s, r);
         };
-        if (Nb < N) {                                   // right strip: all M rows, columns [Nb, N)
-            q = sp;
-            q.g.N = N - Nb;
-            q.B = B + (size_t)Nb * ldb;
-            q.g.C = C + Nb;
-            q.g.epi = epi_block(p.epi, 0, Nb);
-            q.g.bias = bias ? bias + Nb : nullptr;
-            strip(q);
-        }
-        if (Mb < M) {                                   // bottom strip: rows [Mb, M), columns [0, Nb)
-            q = sp;
-            q.g.M = M - Mb; q.g.N = Nb;
-            q.A = A + (size_t)Mb * lda;
-            q.g.C = C + (size_t)Mb * ldc;
-            q.g.epi = epi_block(p.epi, Mb, 0);
-            strip(q);
-        }
+        if (Nb < N) strip(right_strip(sp, Nb));
+        if (Mb < M) strip(bottom_strip(sp, Mb, Nb));
         LC_CHECK_LAUNCH("lc_gemm_bf16_nt (256 x 256 tiles)");
-        if (nsl > 1) {
-            const size_t quads = (size_t)M * N / 4;
-            int g = (int)((quads + 255) / 256);
-            if (g > 2048) g = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, s, (float *)workspace, nsl, M, N, alpha, beta, C, ldc, bias);
-            LC_CHECK_LAUNCH("splitk_reduce");
-        }
-        return LC_OK;
+        return splitk_reduce(ks, M, N, alpha, beta, C, ldc, bias, s);
     }
-    int nsl = pick_splitk(M, N, K);
-    if (nsl > 1 && (!workspace || workspace_bytes < (size_t)nsl * M * N * sizeof(float))) nsl = 1;
-    p.kchunk = nsl > 1 ? lc_cdiv(lc_cdiv(K, nsl), SBK) * SBK : (K > 0 ? K : 1);
-    if (nsl > 1) nsl = lc_cdiv(K, p.kchunk);
-    p.slab = nsl > 1 ? (float *)workspace : nullptr;
-    p.slab_slice = (size_t)M * N;
-    p.slab_ld = N;
-    auto launch = [&](bool fast, const SGemmArgs &q) {
-        const long long nwg = (long long)lc_cdiv(q.g.M, BM) * lc_cdiv(q.g.N, BN);
-        dim3 grid((unsigned)nwg, 1, (unsigned)(nsl > 1 ? nsl : 1)), block(NT);
-        if (fast) hipLaunchKernelGGL((gemm_bf16s_kernel<true>), grid, block, 0, s, q);
-        else hipLaunchKernelGGL((gemm_bf16s_kernel<false>), grid, block, 0, s, q);
-    };
-    const bool kfast = K > 0 && (K % SBK == 0) && (p.kchunk % SBK == 0);
+    const KSplit ks = plan_ksplit(pick_splitk(M, N, K), M, N, K, SBK, epi, workspace, workspace_bytes);
+    set_ksplit(sp.g, ks);
+    const bool kfast = K > 0 && (K % SBK == 0) && (ks.kchunk % SBK == 0);
     const int Mi = M / BM * BM, Ni = N / BN * BN;
     if (kfast && Mi > 0 && Ni > 0) {                 // interior without bounds checks, ragged edges as strips
         SGemmArgs q = sp;
         q.g.M = Mi; q.g.N = Ni;
-        launch(true, q);
-        if (Ni < N) {
-            q = sp;
-            q.g.N = N - Ni;
-            q.B = B + (size_t)Ni * ldb;
-            q.g.C = C + Ni;
-            q.g.epi = epi_block(p.epi, 0, Ni);
-            q.g.bias = bias ? bias + Ni : nullptr;
-            if (q.g.slab) q.g.slab += Ni;
-            launch(false, q);
-        }
-        if (Mi < M) {
-            q = sp;
-            q.g.M = M - Mi; q.g.N = Ni;
-            q.A = A + (size_t)Mi * lda;
-            q.g.C = C + (size_t)Mi * ldc;
-            q.g.epi = epi_block(p.epi, Mi, 0);
-            if (q.g.slab) q.g.slab += (size_t)Mi * N;
-            launch(false, q);
-        }
+        launch_bf16s(true, ks.nsl, s, q);
+        if (Ni < N) launch_bf16s(false, ks.nsl, s, right_strip(sp, Ni));
+        if (Mi < M) launch_bf16s(false, ks.nsl, s, bottom_strip(sp, Mi, Ni));
     } else {
-        launch(false, sp);
+        launch_bf16s(false, ks.nsl, s, sp);
     }
     LC_CHECK_LAUNCH("lc_gemm_bf16_nt");
-    if (nsl > 1) {
-        const size_t quads = (size_t)M * N / 4;
-        int g = (int)((quads + 255) / 256);
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, s, p.slab, nsl, M, N, alpha, beta, C, ldc, bias);
-        LC_CHECK_LAUNCH("splitk_reduce");
-    }
-    return LC_OK;
+    return splitk_reduce(ks, M, N, alpha, beta, C, ldc, bias, s);
+}
+
+static void launch_bf16s(bool fast, int nsl, hipStream_t s, const SGemmArgs &q)
+{
+    const long long nwg = (long long)lc_cdiv(q.g.M, BM) * lc_cdiv(q.g.N, BN);
+    const dim3 grid((unsigned)nwg, 1, (unsigned)nsl), block(NT);
+    if (fast) hipLaunchKernelGGL((gemm_bf16s_kernel<true>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((gemm_bf16s_kernel<false>), grid, block, 0, s, q);
 }
 
 extern "C" int lc_gemm_bf16_nt(int M, int N, int K, float alpha, const uint16_t *A, int lda, const uint16_t *B, int ldb,
@@ -1848,7 +1829,6 @@ static int gemm_bf16_kmajor(bool acol, const char *who, int M, int N, int K, flo
                             size_t workspace_bytes, lc_stream_t stream)
 {
     const EpiArgs epi = epi_take();
-    if (epi_active(epi)) { workspace = nullptr; workspace_bytes = 0; }      // fused epilogue: no K split
     LC_CHECK_ARG(A && B && C, "%s: null pointer", who);
     LC_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: empty product", who);
     LC_CHECK_ARG(M % GBM == 0 && N % GBN == 0, "%s: M and N must be multiples of 256 (got %d x %d)", who, M, N);
@@ -1857,43 +1837,21 @@ static int gemm_bf16_kmajor(bool acol, const char *who, int M, int N, int K, flo
     LC_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && aligned16(A) && aligned16(B),
                  "%s: lda, ldb must be multiples of 8 and the operands 16-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
-    SGemmArgs sp;
-    GemmArgs &p = sp.g;
-    p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta;
-    p.A = nullptr; p.lda = lda; p.B = nullptr; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias;
-    p.vecA = p.vecB = 1;
-    p.epi = epi;
-    sp.A = A; sp.B = B;
-    int nsl = pick_splitk_big(M, N, K);
-    if (nsl > 1 && (!workspace || workspace_bytes < (size_t)nsl * M * N * sizeof(float))) nsl = 1;
-    p.kchunk = nsl > 1 ? lc_cdiv(lc_cdiv(K, nsl), GBK) * GBK : K;
-    if (nsl > 1) nsl = lc_cdiv(K, p.kchunk);
+    SGemmArgs sp = sgemm_args(epi, M, N, K, alpha, beta, A, lda, B, ldb, C, ldc, bias);
+    const KSplit ks = plan_ksplit(pick_splitk_big(M, N, K), M, N, K, GBK, epi, workspace, workspace_bytes);
+    set_ksplit(sp.g, ks);
     // 32-bit byte offsets inside a K chunk: (k tile) * 64 rows * ld * 2 bytes (K-major operands); rows * ld (k-contiguous)
-    LC_CHECK_ARG((long long)p.kchunk * (acol && lda > ldb ? lda : ldb) * 2 < 0x7fffffffll &&
+    LC_CHECK_ARG((long long)ks.kchunk * (acol && lda > ldb ? lda : ldb) * 2 < 0x7fffffffll &&
                      (acol || (long long)(GBM - 1) * lda * 2 + 2ll * K < 0x7fffffffll), "%s: operand too large", who);
-    p.slab = nsl > 1 ? (float *)workspace : nullptr;
-    p.slab_slice = (size_t)M * N;
-    p.slab_ld = N;
     const long long tiles = (long long)(M / GBM) * (N / GBN);
-    const dim3 grid((unsigned)tiles, 1, (unsigned)(nsl > 1 ? nsl : 1));
-    const bool persist = bf16g_persist_ok(tiles, nsl, K);
-    const dim3 pgrid((unsigned)lc_num_cus(), 1, 1);
-    if (acol) {
-        if (persist) hipLaunchKernelGGL((gemm_bf16g_kernel<true, true, true>), pgrid, dim3(GNT), 0, s, sp);
-        else hipLaunchKernelGGL((gemm_bf16g_kernel<true, true>), grid, dim3(GNT), 0, s, sp);
-    } else {
-        if (persist) hipLaunchKernelGGL((gemm_bf16g_kernel<false, true, true>), pgrid, dim3(GNT), 0, s, sp);
-        else hipLaunchKernelGGL((gemm_bf16g_kernel<false, true>), grid, dim3(GNT), 0, s, sp);
-    }
+    const dim3 grid((unsigned)tiles, 1, (unsigned)ks.nsl), pgrid((unsigned)lc_num_cus(), 1, 1), block(GNT);
+    const bool persist = bf16g_persist_ok(tiles, ks.nsl, K);
+    if (acol && persist) hipLaunchKernelGGL((gemm_bf16g_kernel<true, true, true>), pgrid, block, 0, s, sp);
+    else if (acol) hipLaunchKernelGGL((gemm_bf16g_kernel<true, true>), grid, block, 0, s, sp);
+    else if (persist) hipLaunchKernelGGL((gemm_bf16g_kernel<false, true, true>), pgrid, block, 0, s, sp);
+    else hipLaunchKernelGGL((gemm_bf16g_kernel<false, true>), grid, block, 0, s, sp);
     LC_CHECK_LAUNCH(who);
-    if (nsl > 1) {
-        const size_t quads = (size_t)M * N / 4;
-        int g = (int)((quads + 255) / 256);
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(g), dim3(256), 0, s, (float *)workspace, nsl, M, N, alpha, beta, C, ldc, bias);
-        LC_CHECK_LAUNCH("splitk_reduce");
-    }
-    return LC_OK;
+    return splitk_reduce(ks, M, N, alpha, beta, C, ldc, bias, s);
 }
 
 extern "C" int lc_gemm_bf16_tn(int M, int N, int K, float alpha, const uint16_t *A, int lda, const uint16_t *B, int ldb,

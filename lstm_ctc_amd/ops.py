@@ -138,11 +138,17 @@ def _f32c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _ld(t):
+    """Leading dimension of a 2-D view whose last stride is 1: its row stride - which torch leaves arbitrary on a single row,
+    so there at least the row's width."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
 def _rowmajor2d(t):
     assert t.dim() == 2 and t.dtype == torch.float32
     if t.stride(1) != 1:
         t = t.contiguous()
-    return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+    return t, _ld(t)
 
 
 # ------------------------------------------------------------------------------------------ GEMM
@@ -164,36 +170,51 @@ def _arm(lib, epilogue, out):
         _require_cuda(sh)
         assert sh.dtype == torch.bfloat16 and sh.shape == out.shape and sh.stride(1) == 1
     e = _lib.GemmEpilogue(epilogue.keep, epilogue.seed & 0xFFFFFFFF, epilogue.stream0, epilogue.width,
-                          _ptr(sh), (sh.stride(0) if sh.shape[0] > 1 else max(sh.stride(0), sh.shape[1])) if sh is not None else 0,
+                          _ptr(sh), _ld(sh) if sh is not None else 0,
                           int(getattr(epilogue, "shadow_only", False)))
     _lib.check(lib.lc_gemm_next_epilogue(ctypes.byref(e)), "lc_gemm_next_epilogue")
+
+
+def _product(name, kind, head, M, N, Ks, A, B, out, alpha, beta, bias, epilogue=None, dtype=torch.bfloat16, pool=None,
+             nbytes=0):
+    """out[M,N] = alpha * (what lc_<name> makes of A and B) + beta*out (+ bias): the one path under every product wrapper.
+    A, B: tuples of 2-D `dtype` views with last stride 1 (dtype None: the caller has normalised them, _rowmajor2d) - one operand
+    each, or the two of an nt2 product, which share their row stride.  The entry's arguments are head, M, N, Ks, alpha, A.., lda, B.., ldb, beta, out, ldc, bias, then the workspace
+    if it takes one (pool: its name here; "gemm" is sized by lc_gemm_workspace_bytes, any other by nbytes), then the stream.
+    sum(Ks) is the reduction depth of the FLOP count under the profiling kind."""
+    lib = _lib.load()
+    _require_cuda(*A, *B, out, bias)
+    for t in A + B if dtype is not None else ():
+        assert t.dim() == 2 and t.dtype == dtype and t.stride(1) == 1, (t.dtype, tuple(t.shape), t.stride())
+    if out is None:
+        assert beta == 0.0
+        out = torch.empty((M, N), dtype=torch.float32, device=A[0].device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
+    args = [*head, M, N, *Ks, alpha, *map(_ptr, A), _ld(A[0]), *map(_ptr, B), _ld(B[0]), beta, _ptr(out), _ld(out), _ptr(bias)]
+    if pool is not None:
+        if pool == "gemm":
+            nbytes = lib.lc_gemm_workspace_bytes(M, N, sum(Ks))
+        ws = workspace(pool, nbytes, A[0].device) if nbytes else None
+        args += [_ptr(ws), nbytes]
+    ev = _prof_begin()
+    _arm(lib, epilogue, out)
+    _lib.check(getattr(lib, name)(*args, _stream()), name)
+    _prof_end(kind, 2.0 * M * N * sum(Ks), ev)
+    return out
 
 
 def gemm(A, B, ta=False, tb=False, out=None, alpha=1.0, beta=0.0, bias=None, bf16=False, epilogue=None):
     """out[M,N] = alpha * op(A) @ op(B) + beta*out (+ bias).  A/B/out are 2-D row-major views whose
     last stride is 1 (row stride free, so column slices of wider buffers are fine).
     bf16=True: operands rounded to bf16 on load, fp32 accumulate (lc_gemm_bf16; config c5)."""
-    lib = _lib.load()
     _require_cuda(A, B, out, bias)
-    A, lda = _rowmajor2d(A)
-    B, ldb = _rowmajor2d(B)
+    A, B = _rowmajor2d(A)[0], _rowmajor2d(B)[0]
     M, K = (A.shape[1], A.shape[0]) if ta else (A.shape[0], A.shape[1])
     K2, N = (B.shape[1], B.shape[0]) if tb else (B.shape[0], B.shape[1])
     assert K == K2, (A.shape, B.shape, ta, tb)
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
-    nbytes = lib.lc_gemm_workspace_bytes(M, N, K)
-    ws = workspace("gemm", nbytes, A.device) if nbytes else None
-    ev = _prof_begin()
-    fn, who = (lib.lc_gemm_bf16, "lc_gemm_bf16") if bf16 else (lib.lc_gemm_f32, "lc_gemm_f32")
-    _arm(lib, epilogue, out)
-    _lib.check(fn(int(ta), int(tb), M, N, K, alpha, _ptr(A), lda, _ptr(B), ldb, beta, _ptr(out), ldc,
-                  _ptr(bias), _ptr(ws), nbytes, _stream()), who)
-    _prof_end("gemm_bf16" if bf16 else "gemm", 2.0 * M * N * K, ev)
-    return out
+    name, kind = ("lc_gemm_bf16", "gemm_bf16") if bf16 else ("lc_gemm_f32", "gemm")
+    return _product(name, kind, (int(ta), int(tb)), M, N, (K,), (A,), (B,), out, alpha, beta, bias, epilogue, dtype=None,
+                    pool="gemm")
 
 
 def transpose(x):
@@ -955,123 +976,45 @@ def cast_bf16(x, nat=True, tr=False, out_nat=None):
 def gemm_bf16_nt(A, B, out=None, alpha=1.0, beta=0.0, bias=None, K=None, epilogue=None):
     """out[M,N] = alpha * A[M,K] @ B[N,K]^T + beta*out (+ bias) on bf16 shadow operands (k contiguous in both).
     K defaults to A.shape[1] (pass the true K when the operands carry zero pad columns)."""
-    lib = _lib.load()
-    _require_cuda(A, B, out, bias)
-    assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.stride(1) == 1 and B.stride(1) == 1
-    M, N = A.shape[0], B.shape[0]
     K = A.shape[1] if K is None else K
     assert B.shape[1] >= K and A.shape[1] >= K
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    lda = A.stride(0) if M > 1 else max(A.stride(0), A.shape[1])
-    ldb = B.stride(0) if N > 1 else max(B.stride(0), B.shape[1])
-    ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
-    nbytes = lib.lc_gemm_workspace_bytes(M, N, K)
-    ws = workspace("gemm", nbytes, A.device) if nbytes else None
-    ev = _prof_begin()
-    _arm(lib, epilogue, out)
-    _lib.check(lib.lc_gemm_bf16_nt(M, N, K, alpha, _ptr(A), lda, _ptr(B), ldb, beta, _ptr(out), ldc, _ptr(bias),
-                                   _ptr(ws), nbytes, _stream()), "lc_gemm_bf16_nt")
-    _prof_end("gemm_bf16", 2.0 * M * N * K, ev)
-    return out
+    return _product("lc_gemm_bf16_nt", "gemm_bf16", (), A.shape[0], B.shape[0], (K,), (A,), (B,), out, alpha, beta, bias, epilogue,
+                    pool="gemm")
+
+
+def _product_nt2(name, kind, dtype, A1, B1, A2, B2, out, alpha, beta, bias, epilogue):
+    M, N, K1, K2 = A1.shape[0], B1.shape[0], A1.shape[1], A2.shape[1]
+    assert A2.shape[0] == M and B2.shape[0] == N and B1.shape[1] == K1 and B2.shape[1] == K2
+    assert A1.stride(0) == A2.stride(0) and B1.stride(0) == B2.stride(0) and M > 1 and N > 1
+    return _product(name, kind, (), M, N, (K1, K2), (A1, A2), (B1, B2), out, alpha, beta, bias, epilogue, dtype=dtype)
 
 
 def gemm_nt2(A1, B1, A2, B2, out=None, alpha=1.0, beta=0.0, bias=None, epilogue=None):
     """out[M,N] = alpha * (A1 @ B1^T + A2 @ B2^T) + beta*out (+ bias) in one pass over out, float32 (lc_gemm_f32_nt2): A [M,K],
     B [N,K] row-major views with last stride 1, both pairs with the same row strides - the dX of a bidirectional layer."""
-    lib = _lib.load()
-    _require_cuda(A1, B1, A2, B2, out, bias)
-    for t in (A1, B1, A2, B2):
-        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
-    M, N, K1, K2 = A1.shape[0], B1.shape[0], A1.shape[1], A2.shape[1]
-    assert A2.shape[0] == M and B2.shape[0] == N and B1.shape[1] == K1 and B2.shape[1] == K2
-    assert A1.stride(0) == A2.stride(0) and B1.stride(0) == B2.stride(0) and M > 1 and N > 1
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A1.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    ev = _prof_begin()
-    _arm(lib, epilogue, out)
-    _lib.check(lib.lc_gemm_f32_nt2(M, N, K1, K2, alpha, _ptr(A1), _ptr(A2), A1.stride(0), _ptr(B1), _ptr(B2), B1.stride(0),
-                                   beta, _ptr(out), out.stride(0), _ptr(bias), _stream()), "lc_gemm_f32_nt2")
-    _prof_end("gemm", 2.0 * M * N * (K1 + K2), ev)
-    return out
+    return _product_nt2("lc_gemm_f32_nt2", "gemm", torch.float32, A1, B1, A2, B2, out, alpha, beta, bias, epilogue)
 
 
 def gemm_bf16_nt2(A1, B1, A2, B2, out=None, alpha=1.0, beta=0.0, bias=None, epilogue=None):
     """out[M,N] = alpha * (A1 @ B1^T + A2 @ B2^T) + beta*out (+ bias) in one pass over out (lc_gemm_bf16_nt2): bf16 shadow
     operands, k contiguous, both pairs with the same row strides - the dX of a bidirectional layer."""
-    lib = _lib.load()
-    _require_cuda(A1, B1, A2, B2, out, bias)
-    for t in (A1, B1, A2, B2):
-        assert t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1
-    M, N, K1, K2 = A1.shape[0], B1.shape[0], A1.shape[1], A2.shape[1]
-    assert A2.shape[0] == M and B2.shape[0] == N and B1.shape[1] == K1 and B2.shape[1] == K2
-    assert A1.stride(0) == A2.stride(0) and B1.stride(0) == B2.stride(0) and M > 1 and N > 1
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A1.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    ev = _prof_begin()
-    _arm(lib, epilogue, out)
-    _lib.check(lib.lc_gemm_bf16_nt2(M, N, K1, K2, alpha, _ptr(A1), _ptr(A2), A1.stride(0), _ptr(B1), _ptr(B2), B1.stride(0),
-                                    beta, _ptr(out), out.stride(0), _ptr(bias), _stream()), "lc_gemm_bf16_nt2")
-    _prof_end("gemm_bf16", 2.0 * M * N * (K1 + K2), ev)
-    return out
+    return _product_nt2("lc_gemm_bf16_nt2", "gemm_bf16", torch.bfloat16, A1, B1, A2, B2, out, alpha, beta, bias, epilogue)
 
 
 def gemm_bf16_tn(A, B, out=None, alpha=1.0, beta=0.0, bias=None, epilogue=None):
     """out[M,N] = alpha * A^T @ B + beta*out (+ bias) on bf16 operands that are both K-MAJOR: A [K,M], B [K,N] (row
     windows of natural-layout shadows are fine: only the last stride must be 1).  M, N multiples of 256."""
-    lib = _lib.load()
-    _require_cuda(A, B, out, bias)
-    assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.stride(1) == 1 and B.stride(1) == 1
     K, M = A.shape
     assert B.shape[0] == K
-    N = B.shape[1]
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    lda = A.stride(0) if K > 1 else max(A.stride(0), M)
-    ldb = B.stride(0) if K > 1 else max(B.stride(0), N)
-    ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
-    nbytes = lib.lc_gemm_workspace_bytes(M, N, K)
-    ws = workspace("gemm", nbytes, A.device) if nbytes else None
-    ev = _prof_begin()
-    _arm(lib, epilogue, out)
-    _lib.check(lib.lc_gemm_bf16_tn(M, N, K, alpha, _ptr(A), lda, _ptr(B), ldb, beta, _ptr(out), ldc, _ptr(bias),
-                                   _ptr(ws), nbytes, _stream()), "lc_gemm_bf16_tn")
-    _prof_end("gemm_bf16", 2.0 * M * N * K, ev)
-    return out
+    return _product("lc_gemm_bf16_tn", "gemm_bf16", (), M, B.shape[1], (K,), (A,), (B,), out, alpha, beta, bias, epilogue, pool="gemm")
 
 
 def gemm_bf16_nn(A, B, out=None, alpha=1.0, beta=0.0, bias=None, epilogue=None):
     """out[M,N] = alpha * A @ B + beta*out (+ bias) on bf16 operands in their NATURAL layouts: A [M,K] (k contiguous), B [K,N]
     (K-major).  M, N multiples of 256, K of 64."""
-    lib = _lib.load()
-    _require_cuda(A, B, out, bias)
-    assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.stride(1) == 1 and B.stride(1) == 1
     M, K = A.shape
     assert B.shape[0] == K
-    N = B.shape[1]
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    lda = A.stride(0) if M > 1 else max(A.stride(0), K)
-    ldb = B.stride(0) if K > 1 else max(B.stride(0), N)
-    ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
-    nbytes = lib.lc_gemm_workspace_bytes(M, N, K)
-    ws = workspace("gemm", nbytes, A.device) if nbytes else None
-    ev = _prof_begin()
-    _arm(lib, epilogue, out)
-    _lib.check(lib.lc_gemm_bf16_nn(M, N, K, alpha, _ptr(A), lda, _ptr(B), ldb, beta, _ptr(out), ldc, _ptr(bias),
-                                   _ptr(ws), nbytes, _stream()), "lc_gemm_bf16_nn")
-    _prof_end("gemm_bf16", 2.0 * M * N * K, ev)
-    return out
+    return _product("lc_gemm_bf16_nn", "gemm_bf16", (), M, B.shape[1], (K,), (A,), (B,), out, alpha, beta, bias, epilogue, pool="gemm")
 
 
 # ------------------------------------------------------------------------------------------ fp32 products as bf16 x 3
@@ -1093,44 +1036,15 @@ def split_bf16x3(x):
 def gemm_bf16x3_nt(A3, B3, K, out=None, alpha=1.0, beta=0.0, bias=None, epilogue=None):
     """out[M,N] = alpha * A @ B^T + beta*out (+ bias) from the x3 shadows of A [M,K] and B [N,K]: fp32-grade result on the
     bf16 matrix cores (six bf16 term products per element product)."""
-    lib = _lib.load()
-    _require_cuda(A3, B3, out, bias)
-    assert A3.dtype == torch.bfloat16 and B3.dtype == torch.bfloat16 and A3.stride(1) == 1 and B3.stride(1) == 1
-    M, N = A3.shape[0], B3.shape[0]
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A3.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    lda = A3.stride(0) if M > 1 else max(A3.stride(0), A3.shape[1])
-    ldb = B3.stride(0) if N > 1 else max(B3.stride(0), B3.shape[1])
-    ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
-    ev = _prof_begin()
-    _arm(lib, epilogue, out)
-    _lib.check(lib.lc_gemm_bf16x3_nt(M, N, K, alpha, _ptr(A3), lda, _ptr(B3), ldb, beta, _ptr(out), ldc, _ptr(bias),
-                                     _stream()), "lc_gemm_bf16x3_nt")
-    _prof_end("gemm_x3", 2.0 * M * N * K, ev)
-    return out
+    return _product("lc_gemm_bf16x3_nt", "gemm_x3", (), A3.shape[0], B3.shape[0], (K,), (A3,), (B3,), out, alpha, beta, bias, epilogue)
 
 
 def gemm_bf16x3_tn(A3, B3, M, N, out=None, alpha=1.0, beta=0.0, bias=None):
     """out[M,N] = alpha * A^T @ B + beta*out (+ bias) from the x3 shadows of A [K,M] and B [K,N] (both K-major; row windows
     of larger shadows are fine): the weight gradients, fp32-grade, on the bf16 matrix cores."""
-    lib = _lib.load()
-    _require_cuda(A3, B3, out, bias)
-    assert A3.dtype == torch.bfloat16 and B3.dtype == torch.bfloat16 and A3.stride(1) == 1 and B3.stride(1) == 1
     K = A3.shape[0]
     assert B3.shape[0] == K and A3.shape[1] >= 3 * ((M + 15) // 16 * 16) and B3.shape[1] >= 3 * ((N + 15) // 16 * 16)
-    if out is None:
-        assert beta == 0.0
-        out = torch.empty((M, N), dtype=torch.float32, device=A3.device)
-    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
-    lda = A3.stride(0) if K > 1 else max(A3.stride(0), A3.shape[1])
-    ldb = B3.stride(0) if K > 1 else max(B3.stride(0), B3.shape[1])
-    ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
-    nbytes = lib.lc_gemm_bf16x3_tn_workspace_bytes_ld(M, N, K, lda, ldb)     # K slices: CU fill, and the 2 GB descriptor reach
-    ws = workspace("gemm_x3", nbytes, A3.device) if nbytes else None
-    ev = _prof_begin()
-    _lib.check(lib.lc_gemm_bf16x3_tn(M, N, K, alpha, _ptr(A3), lda, _ptr(B3), ldb, beta, _ptr(out), ldc, _ptr(bias),
-                                     _ptr(ws), nbytes, _stream()), "lc_gemm_bf16x3_tn")
-    _prof_end("gemm_x3", 2.0 * M * N * K, ev)
-    return out
+    # K slices: CU fill, and the 2 GB descriptor reach
+    nbytes = _lib.load().lc_gemm_bf16x3_tn_workspace_bytes_ld(M, N, K, _ld(A3), _ld(B3))
+    return _product("lc_gemm_bf16x3_tn", "gemm_x3", (), M, N, (K,), (A3,), (B3,), out, alpha, beta, bias, pool="gemm_x3",
+                    nbytes=nbytes)
