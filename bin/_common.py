@@ -213,6 +213,65 @@ def report_entropy_weight(graph):
                % (graph.entropy_weight, graph.path_entropy_total / max(n, 1), n))
 
 
+def parse_star_penalty(text):
+    """'B[,S]' -> (bypass_penalty, selfloop_penalty); one value sets both, 'inf' is accepted.  ValueError for anything else,
+    for NaN and for a negative value."""
+    parts = [p.strip() for p in text.split(',')]
+    if len(parts) not in (1, 2):
+        raise ValueError('expected B or B,S')
+    values = tuple(float(p) for p in parts)              # '' and words raise here
+    if not all(v >= 0 for v in values):                  # NaN fails the comparison
+        raise ValueError('a penalty must be >= 0 or inf')
+    return values * 2 if len(values) == 1 else values
+
+
+def star_keywords(args):
+    """--star-penalty: the graph keyword, empty without the flag (nnet-init has none).  The FATAL line and exit 1 when the
+    value is not B[,S] with penalties >= 0 or inf, meets another objective than ctc, or comes with --delay-penalty or
+    --entropy-weight.  Host work only: runs BEFORE the device is set up."""
+    text = getattr(args, 'star_penalty', None)
+    if text is None:
+        return {}
+    try:
+        penalty = parse_star_penalty(text)
+    except ValueError as e:
+        _fatal('--star-penalty must be B[,S] with penalties >= 0 or inf, got %r (%s)' % (text, e))
+    if args.objective != 'ctc':
+        _fatal('--star-penalty relaxes the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
+    for other in ('delay_penalty', 'entropy_weight'):
+        if getattr(args, other, None) is not None:
+            _fatal('--star-penalty does not combine with --%s (the star under that term is not built)' % other.replace('_', '-'))
+    return {'star_penalty': penalty}
+
+
+def report_star_penalty(graph):
+    """One INFO line at the end of a pass under --star-penalty: the share of the frames the star explains under the
+    criterion's path posterior."""
+    from lstm_ctc_amd.nnet import tflog
+    n = graph.star_frame_count_total
+    tflog.info('star penalty bypass %g selfloop %g: %.6f of %d frame(s) explained by the star'
+               % (graph.star_penalty[0], graph.star_penalty[1], graph.star_frames_total / max(n, 1), n))
+
+
+def star_report_keywords(args):
+    """nnet-align's --star-penalty / --star-report: the keyword of ``CTCGraph.align``, empty without the flags.  The FATAL line
+    and exit 1 for either flag without the other and for a bad penalty, before the device is touched."""
+    text, report = getattr(args, 'star_penalty', None), getattr(args, 'star_report', None)
+    if text is None and report is None:
+        return {}
+    if text is None or report is None:
+        _fatal('--star-penalty and --star-report go together: the report is what the penalty is for')
+    try:
+        return {'star_penalty': parse_star_penalty(text)}
+    except ValueError as e:
+        _fatal('--star-penalty must be B[,S] with penalties >= 0 or inf, got %r (%s)' % (text, e))
+
+
+def star_report_line(key, frames, labels, ctc_loss, star_loss, star_frames):
+    """One line of nnet-align's --star-report: key frames labels ctc_loss star_loss star_frames."""
+    return '%s %d %d %.6f %.6f %.6f\n' % (key, frames, labels, ctc_loss, star_loss, star_frames)
+
+
 def spec_augment_keywords(args):
     """--spec-augment: the graph keyword, empty without the flag.  The FATAL line and exit 1 for a value that
     nnet.augment.parse_spec refuses, and for bins that do not divide the input_dim of a readable <nnet-config>.  Host work
@@ -341,6 +400,15 @@ FLAGS = {
                              'the entropy of the posterior over the feasible paths from the CTC loss, so that the model does not '
                              'collapse onto a few spiky alignments; needs no table, composes with --align-window, not with '
                              '--delay-penalty; 0 is plain CTC and reports the mean path entropy in nats per frame'),
+    '--star-penalty': dict(type=str, default=None, help='B[,S]: transcript-tolerant CTC (new): every lattice position may explain '
+                           'a frame by a star, "some non-blank class", instead of its own class - a label position at penalty B (a '
+                           'substituted or inserted label), a blank position at penalty S (a deleted label; one value sets both, inf '
+                           'switches one off); with --objective ctc in nnet-train / nnet-validate it is the criterion, composes with '
+                           '--align-window, not with --delay-penalty / --entropy-weight, and reports the share of frames the star '
+                           'explains; in nnet-align it goes with --star-report'),
+    '--star-report': dict(type=str, default=None, help='with --star-penalty (new: nnet-align): write text lines "key frames labels '
+                          'ctc_loss star_loss star_frames" here, one per utterance with labels that fit its frames - a large '
+                          'star_frames marks a suspect transcript'),
     '--spec-augment': dict(type=str, default=None, help='SpecAugment on the device, training steps only (new): '
                            'time=NxW,freq=NxW,bins=F[,cap=P][,fill=V] = N time masks of at most W raw frames (and at most P percent '
                            'of the utterance, default 100), N frequency masks of at most W of the F bins of a feature group '

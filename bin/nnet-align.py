@@ -6,11 +6,12 @@ scp order.  An utterance without labels, or whose labels do not fit its frames, 
 import os
 import sys
 
-from _common import build_cli, setup_device, report_chunking
+from _common import build_cli, setup_device, report_chunking, star_report_keywords, star_report_line
 
 
 def main(args):
     import numpy as np
+    tolerant = star_report_keywords(args)                 # --star-penalty / --star-report; fatal before the device is touched
     device, _, _, _ = setup_device()
     import lstm_ctc_amd.nnet as nnet
     from lstm_ctc_amd import ops
@@ -19,6 +20,7 @@ def main(args):
     writer = Int32VectorWriter(args.alignment)
     segments = open(args.segments, "w") if args.segments else None
     scores = open(args.scores, "w") if args.scores else None
+    report = open(args.star_report, "w") if tolerant else None
     nnet_config = nnet.parse_config(args.nnet_config)
     nnet_config['is_training'] = False
     report_chunking(nnet_config)                          # chunk_frames / lookahead_frames: one INFO line
@@ -47,13 +49,16 @@ def main(args):
                 x[b, :p["nnet_input"].shape[0]] = p["nnet_input"]
                 y[b, :len(p["nnet_target"])] = p["nnet_target"]
             seq = np.asarray([p["nnet_input"].shape[0] for p in pending], np.int32)
-            out = graph.align({"nnet_input": x, "nnet_target": y, "sequence_length": seq})
+            out = graph.align({"nnet_input": x, "nnet_target": y, "sequence_length": seq}, **tolerant)
             segs = ops.alignment_segments(out["ali"], out["label_index"], seq) if segments else None
             dog.kick()                 # the device part of the batch is done ...
             dog.pause()                # ... and back-pressure from whoever reads the table is not a hang
             for b, p in enumerate(pending):
                 key, _ = os.path.splitext(os.path.basename(p["filename"]))
                 processed += 1
+                if report and 0 < len(p["nnet_target"]) <= seq[b]:
+                    report.write(star_report_line(key, seq[b], len(p["nnet_target"]), float(out["ctc_loss"][b]),
+                                                  float(out["star_loss"][b]), float(out["star_frames"][b])))
                 if len(p["nnet_target"]) == 0:
                     tflog.info('WARNING: %s has no labels, skipped' % key)
                     skipped += 1
@@ -85,13 +90,13 @@ def main(args):
     finally:
         dog.stop()
     writer.Close()
-    for f in (segments, scores):
+    for f in (segments, scores, report):
         if f is not None:
             f.close()
 
 
 if __name__ == '__main__':
     args = build_cli(('tfrecords_scp', 'nnet_config', 'nnet_in', 'alignment'),
-                     ('--batch-utts', '--report-interval', '--segments', '--scores')).parse_args()
+                     ('--batch-utts', '--report-interval', '--segments', '--scores', '--star-penalty', '--star-report')).parse_args()
     sys.stderr.write('INFO:tensorflow:' + ' '.join(sys.argv) + '\n')
     main(args)

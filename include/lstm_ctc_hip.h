@@ -172,6 +172,44 @@ int lc_ctc_loss_entropy(const float *logits, int T, int B, int V, const int *lab
                         float entropy_weight, float *loss, float *entropy, float *grad,
                         void *workspace, size_t workspace_bytes, lc_stream_t stream);
 
+/* Transcript-tolerant CTC (after OTC / BTC, Gao et al. 2023, and STC, Pratap et al. 2022): the CTC criterion on a lattice whose
+ * every position may explain a frame by a penalised star symbol, "some non-blank class", instead of by its own class, and
+ * the expected number of frames the star explains.  No reference counterpart.  Everything not said here is
+ * lc_ctc_loss_windowed's contract (blank = V-1, ctc_merge_repeated transitions, a path starts in position 0 or 1 and ends in
+ * S-1 or S-2).  With q = softmax(logits[t,b,:]), Qnb(t) = sum_{k < V-1} q_k and qstar(t) = Qnb(t) / (V - 1), the emission of
+ * lattice position s at frame t is the mixture e'(t, s) = q_y(t) + exp(-bypass_penalty) qstar(t) at a label position of
+ * class y (the label may be bypassed: a substituted or inserted label) and q_blank(t) + exp(-selfloop_penalty) qstar(t) at a
+ * blank position (the blank may absorb speech: a deleted label); Z = sum over the feasible paths of prod_t e'(t, s_t):
+ *   win_lo, win_hi  both NULL = unconstrained; else lc_ctc_loss_windowed's windows (exactly one NULL is LC_EINVAL);
+ *   bypass_penalty, selfloop_penalty  each >= 0 or +inf (NaN, negative, -inf -> LC_EINVAL, nothing is launched); +inf
+ *                   switches that star off;
+ *   loss [B]        -log Z, natural log.  It MAY BE NEGATIVE: e' is not normalised over the classes;
+ *   star_frames [B] required: sum_t M(t), M(t) = sum_s occupancy(t, s) sigma(t, s), sigma = the star's share of e': the
+ *                   expected number of frames explained by the star under the path posterior; equally d loss / d p when
+ *                   both penalties move together, and loss is concave in that p;
+ *   grad [T,B,V]    or NULL: softmax_k - rho_k occ_k - [k < V-1] (q_k / Qnb) M(t), rho = the own share of e', occ_k the
+ *                   occupancy of class k's positions: the exact derivative; live rows sum to 0; +0 for t >= seq_len[b].
+ * With both penalties +inf, loss and grad are lc_ctc_loss_windowed's (with windows) and lc_ctc_loss_delay's at delay_penalty 0
+ * (without), bit for bit, and star_frames is +0.
+ * lc_ctc_loss's conventions: a skipped utterance -> loss 0, star_frames 0, gradient 0; a bad label -> loss NaN, star_frames
+ * NaN, gradient 0; no surviving path -> loss +inf, star_frames 0, gradient = softmax, no NaN anywhere; L = 0 -> the all-blank
+ * path, whose cells still carry the self-loop star.  A frame whose non-blank logits are all -inf has no star.  Every element
+ * of every output is written on every call; results are bit-identical from call to call and loss / star_frames are
+ * bit-identical with and without a gradient (no atomics, fixed summation orders; both sweeps always run).
+ * This is a per-frame mixture, not OTC's WFST: there the star is a separate arc that replaces a label and is then followed
+ * by that star's own self-loops; here the star is an alternative of the CELL at every single frame, so a run of frames in
+ * one position may switch between own class and star frame by frame, the transitions are plain CTC's, and no graph is
+ * composed.  Arithmetic: lc_ctc_loss_windowed's double cells in the log2 domain; the star term is
+ * (lse_nb - lse) log2 e - log2(V - 1) - penalty log2 e with lse_nb a second fp32 log-sum-exp over the non-blank classes
+ * (never log(1 - q_blank)), the constant part formed in double and rounded once; e' = max + log2(1 + 2^-|difference|) on the
+ * fp32 pipes; M(t) and its fold in double, rounded once.
+ * Shapes and errors as for lc_ctc_loss_windowed; the workspace is lc_ctc_loss_delay's plus T * B floats. */
+size_t lc_ctc_star_workspace_bytes(int T, int B, int V, int max_label_len);
+int lc_ctc_loss_star(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                     const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
+                     float bypass_penalty, float selfloop_penalty, float *loss, float *star_frames, float *grad,
+                     void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* Frame-level softmax cross-entropy against one target symbol per frame - the objective that trains on what lc_ctc_align
  * writes.  No reference counterpart (the reference never finished frame-level training).
  *   logits [T,B,V] time-major fp32; targets [B,T] int32 (the layout of lc_ctc_align's ali); seq_len [B].

@@ -34,6 +34,9 @@ SIGNATURES = {
     "lc_ctc_entropy_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "lc_ctc_loss_entropy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                     c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lc_ctc_star_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "lc_ctc_loss_star": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lc_xent_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "lc_xent_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_size_t, c_void_p]),

@@ -282,8 +282,8 @@ extern "C" int lc_ctc_align(const float *logits, int T, int B, int V, const int 
     unsigned *bp = (unsigned *)(w + m.bp);
     const int phases = g_align_phases;
     if (phases & 1) {
-        hipLaunchKernelGGL(lat_lse_kernel, dim3(lc_cdiv((long long)T * B, 4)), dim3(256), 0, s, logits, T, B, V, seq_len,
-                           lse);
+        hipLaunchKernelGGL(lat_lse_kernel<false>, dim3(lc_cdiv((long long)T * B, 4)), dim3(256), 0, s, logits, T, B, V, seq_len,
+                           lse, (float *)nullptr);
         LC_CHECK_LAUNCH("ctc_align_lse");
     }
 #define LC_AL(PPL)                                                                                                   \

@@ -1,5 +1,6 @@
-// ctc_lattice.h — what the double-cell log2-domain CTC lattices share (ctc_lattice.hip: windowed, delay-penalised and
-// maximum-entropy CTC, ctc_align.hip: forced alignment; DESIGN.md sections 3.6, 3.8, 3.14): the per-frame log-sum-exp kernel, -inf as "log zero", the
+// ctc_lattice.h — what the double-cell log2-domain CTC lattices share (ctc_lattice.hip: windowed, delay-penalised,
+// maximum-entropy and transcript-tolerant CTC, ctc_align.hip: forced alignment; DESIGN.md sections 3.6, 3.8, 3.14, 3.15): the
+// per-frame log-sum-exp kernel (with the non-blank log-sum-exp beside it for the star), -inf as "log zero", the
 // log-sum-exp of a cell's predecessors on the fp32 exp2 / log2 pipes relative to their maximum, the DPP neighbour shift.
 #pragma once
 #include "common.h"
@@ -12,8 +13,14 @@
 namespace {
 
 // one wave per live frame (t, b): lse[t, b] = log sum_k exp(logits[t, b, k]), fp32.  Grid: ceil(T * B / 4) blocks of 256.
+// NB (transcript-tolerant CTC) also writes lse_nb[t, b] = log sum_{k < V-1} exp(logits[t, b, k]) from the same two passes over the
+// row: a second log-sum-exp around the non-blank maximum, not log(1 - q_blank), which cancels when the blank dominates.  A row
+// whose non-blank logits are all -inf gives -inf (the maximum is clamped to -FLT_MAX, so no -inf - -inf arises).  lse is
+// formed by the same operations in the same order with and without NB.
+template <bool NB>
 __global__ __launch_bounds__(256) void lat_lse_kernel(const float *__restrict__ logits, int T, int B, int V,
-                                                      const int *__restrict__ seq_len, float *__restrict__ lse)
+                                                      const int *__restrict__ seq_len, float *__restrict__ lse,
+                                                      float *__restrict__ lse_nb)
 {
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -21,13 +28,24 @@ __global__ __launch_bounds__(256) void lat_lse_kernel(const float *__restrict__ 
     const int t = (int)(row / B), b = (int)(row % B);
     if (t >= seq_len[b]) return;                                  // never read
     const float *x = logits + row * V;
-    float m = -INFINITY;
-    for (int k = lane; k < V; k += 64) m = fmaxf(m, x[k]);
+    float m = -INFINITY, mn = -FLT_MAX;
+    for (int k = lane; k < V; k += 64) {
+        m = fmaxf(m, x[k]);
+        if (NB && k < V - 1) mn = fmaxf(mn, x[k]);
+    }
     m = lc_wave_max(m);
-    float s = 0.0f;
-    for (int k = lane; k < V; k += 64) s += __builtin_amdgcn_exp2f((x[k] - m) * LAT_LOG2E);
+    if (NB) mn = lc_wave_max(mn);
+    float s = 0.0f, sn = 0.0f;
+    for (int k = lane; k < V; k += 64) {
+        s += __builtin_amdgcn_exp2f((x[k] - m) * LAT_LOG2E);
+        if (NB && k < V - 1) sn += __builtin_amdgcn_exp2f((x[k] - mn) * LAT_LOG2E);
+    }
     s = lc_wave_sum(s);
-    if (lane == 0) lse[row] = m + __builtin_amdgcn_logf(s) * (float)LAT_LN2;
+    if (NB) sn = lc_wave_sum(sn);
+    if (lane == 0) {
+        lse[row] = m + __builtin_amdgcn_logf(s) * (float)LAT_LN2;
+        if (NB) lse_nb[row] = mn + __builtin_amdgcn_logf(sn) * (float)LAT_LN2;
+    }
 }
 
 __device__ __forceinline__ double lat_neg_inf() { return __longlong_as_double(0xfff0000000000000ull); }
@@ -81,6 +99,12 @@ __device__ __forceinline__ double lat_lse3_mean(double a, double b, double c, do
     mean = ref + ((double)wa * (ma - ref) + (double)wb * (mb - ref) + (double)wc * (mc - ref)) *
                      (double)__builtin_amdgcn_rcpf(sum);
     return m + (double)__builtin_amdgcn_logf(sum);
+}
+// transcript-tolerant CTC: log2(2^e + 2^es), a cell's own emission e mixed with its star term es, on the fp32 pipes.  A star
+// term of -inf (weight 0, or no non-blank mass on the frame) leaves e by a select, bit for bit; e = -inf gives es.
+__device__ __forceinline__ float lat_star_mix(float e, float es)
+{
+    return es > -INFINITY ? fmaxf(e, es) + __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(-fabsf(e - es))) : e;
 }
 __device__ __forceinline__ double lat_readlane(double x, int lane)
 {

@@ -1,5 +1,5 @@
-// ctc_lattice.hip — the three CTC criteria that sum over a constrained or re-weighted set of paths, or carry a second quantity
-// along them, on one lattice:
+// ctc_lattice.hip — the four CTC criteria that sum over a constrained or re-weighted set of paths, carry a second quantity
+// along them, or relax what a lattice cell emits, on one lattice:
 //   * alignment-windowed CTC (lc_ctc_loss_windowed): the CTC loss and gradient summed only over the paths that keep every label
 //     inside a window of frames (Senior et al. 2015: windows around a forced alignment stop a unidirectional model emitting
 //     late).  DESIGN.md section 3.8.
@@ -10,13 +10,17 @@
 //   * maximum-entropy CTC (lc_ctc_loss_entropy, Liu et al. 2018): the (windowed) CTC loss, the entropy H = log Z - Ebar of the
 //     posterior over the feasible paths (Ebar = the posterior mean of log p(path)), and the exact gradient of loss - eta H,
 //     with optional label windows.  DESIGN.md section 3.14.
+//   * transcript-tolerant CTC (lc_ctc_loss_star, after OTC / BTC, Gao et al. 2023, and STC, Pratap et al. 2022): every lattice
+//     position may explain a frame by a penalised star, "some non-blank class", instead of by its own class; the loss over
+//     these mixture emissions, the expected number of frames the star explains (star_frames) and the exact gradient, with
+//     optional label windows.  DESIGN.md section 3.15.
 // No reference counterpart.  lc_ctc_loss (ctc.hip) is not touched by this file.
 //
 // Contract (include/lstm_ctc_hip.h): lc_ctc_loss's, plus win_lo / win_hi parallel to the flat labels.  Label j may sit on
 // frame t only when win_lo[j] <= t <= win_hi[j]; blank positions are never constrained.
 //
-// All entries run lat_launch: lse, [index], sweep, [grad<ENTRY, ENT> | entry], [fold] - four launches for the windowed and the
-// entropy loss (two without a gradient).  No LDS atomics, no global atomics, every sum in a fixed order - the result is bit-identical from call
+// All entries run lat_launch: lse, [index], sweep, [grad<ENTRY, ENT, STAR> | entry], [fold] - four launches for the windowed and
+// the entropy loss (two without a gradient), five for the star entry with and without one.  No LDS atomics, no global atomics, every sum in a fixed order - the result is bit-identical from call
 // to call:
 //   1. lat_lse_kernel        (ctc_lattice.h) one wave per live frame (t, b): lse[t, b] = log sum_k exp(logits[t, b, k]), fp32.
 //   2. lat_index_kernel      (gradient only) one workgroup per utterance: the label indices ordered by (class, index), and per
@@ -54,6 +58,13 @@
 //      double, 0 in a dead cell by a select; its rows go to the workspace beside the cells'.  Direction 0 finishes with Ebar
 //      (the end cells' means under the weights of log2 p, to the workspace) and H = (log2 p - Ebar) ln 2 >= 0, in double,
 //      rounded once; a single path gives m == a bit for bit and H = +0.  The windows may be NULL.
+//      STAR (lc_ctc_loss_star; never with DELAY or ENT, the other instantiations carry none of it): only a cell's emission
+//      changes.  The star term of a frame is es = (lse_nb - lse) log2 e - log2(V - 1) - penalty log2 e, lse_nb the frame's
+//      non-blank log-sum-exp (lat_lse_kernel<true>: one more float per frame in the prefetch arrays), the constant part formed
+//      in double on the host and rounded once, one constant for the label positions (bypass) and one for the blank positions
+//      (self-loop); the cell's emission is e' = max(e, es) + log2(1 + 2^-|e - es|) on the fp32 pipes (lat_star_mix), and
+//      e' = e by a select when es = -inf (penalty +inf, or no non-blank mass on the frame).  Windows, dead cells, status words
+//      and the end cells are the plain instantiation's.  The windows may be NULL.
 //   4. lat_grad_kernel<ENTRY, ENT>  one wave per frame.  occupancy(t, s) = 2^(alpha + beta - emission - log2 p), the exponent formed
 //      in double; lane k sums the positions of class k, k + 64, ... in the order of lat_index_kernel's list, the blank's
 //      positions are summed lane by lane and then by the wave's DPP reduction.  grad = softmax - occupancy.  ENTRY also sums
@@ -61,8 +72,11 @@
 //      then a fixed butterfly) into the workspace; without a gradient lat_entry_kernel does the same from the two lattices
 //      alone.  ENT subtracts eta * ln 2 * sum occupancy(t, s) * (Ebar - c(t, s)), c = m_alpha + m_beta - emission the mean log2
 //      probability of the paths through the cell, from the plain gradient: the plain part is summed as without ENT, the
-//      products beside it in double in the same orders.
-//   5. lat_fold_kernel       (entry_sum only) one wave per utterance folds its frame terms in a fixed order in double and rounds
+//      products beside it in double in the same orders.  STAR: the occupancies carry e' in the exponent; the own share
+//      rho = 2^(e - e') scales a class's occupancy sum, the star share sigma = 2^(es - e') gives M(t) = sum_k sigma_k occ_k in
+//      double (to the frame terms, folded into star_frames), and a second pass subtracts 2^((z_k - lse_nb) log2 e) M(t) from
+//      the non-blank classes.  star_frames is required, so this kernel also runs without a gradient and then stores M(t) only.
+//   5. lat_fold_kernel       (entry_sum and star_frames) one wave per utterance folds its frame terms in a fixed order in double and rounds
 //      once.
 // The band (only positions whose window contains t are live) is NOT exploited: every position is computed on every frame.
 #include "common.h"
@@ -117,9 +131,11 @@ __global__ __launch_bounds__(256) void lat_index_kernel(int V, const int *__rest
 }
 
 // ------------------------------------------------------------------------------------------ 3. alpha / beta sweeps
-// DELAY = ENT = false: win_lo / win_hi are not NULL (the host checks).  lambda is read by DELAY alone; malpha / mbeta / ebar /
-// entropy by ENT alone (nullptr otherwise).
-template <int PPL, bool DELAY, bool ENT>
+// DELAY = ENT = STAR = false: win_lo / win_hi are not NULL (the host checks).  lambda is read by DELAY alone; malpha / mbeta /
+// ebar / entropy by ENT alone (nullptr otherwise); lse_nb / star_b / star_s by STAR alone.
+// STAR (lc_ctc_loss_star; never with DELAY or ENT): star_b / star_s = log2(V - 1) + penalty * log2(e) of the bypass (label
+// positions) and the self-loop (blank positions) star, +inf for a penalty of +inf.
+template <int PPL, bool DELAY, bool ENT, bool STAR>
 __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__ logits, int T, int B, int V,
                                                        const int *__restrict__ labels, const int *__restrict__ offs,
                                                        const int *__restrict__ seq_len, int maxL,
@@ -129,8 +145,10 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
                                                        int want_beta, float *__restrict__ loss,
                                                        double *__restrict__ lp2, int *__restrict__ status,
                                                        double *__restrict__ malpha, double *__restrict__ mbeta,
-                                                       double *__restrict__ ebar, float *__restrict__ entropy)
+                                                       double *__restrict__ ebar, float *__restrict__ entropy,
+                                                       const float *__restrict__ lse_nb, float star_b, float star_s)
 {
+    static_assert(!(STAR && (DELAY || ENT)), "the star is built under neither the delay tilt nor the entropy term");
     constexpr int K = PPL <= 4 ? 8 : 32 / PPL;            // frames fetched ahead as one chunk: 8, 8, 8, 4, 2, 1
     constexpr int NG = PPL == 1 ? 1 : PPL / 2;            // label positions (gathers, windows) per lane
     const int b = blockIdx.x >> 1, dir = blockIdx.x & 1, lane = threadIdx.x;
@@ -174,7 +192,7 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
             if ((p & 1) && p < S) {
                 const int i = dir ? L - 1 - (p >> 1) : (p >> 1);          // the label this position stands for
                 sym = labels[off + i];
-                if (!(DELAY || ENT) || win_lo) {
+                if (!(DELAY || ENT || STAR) || win_lo) {
                     lo = win_lo[off + i];
                     hi = win_hi[off + i];
                 }
@@ -196,8 +214,9 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
     for (int j = 0; j < PM; ++j) mm[j] = 0.0;
     const double wl = DELAY ? -(double)lambda * LAT_LOG2E_D : 0.0;       // w(t) = wl * t
 
-    float cg[K][NG], cb[K], cl[K], ng[K][NG], nb[K], nl[K];
-    auto fetch = [&](int k0, float (&g)[K][NG], float (&gb)[K], float (&gl)[K]) {
+    constexpr int KS = STAR ? K : 1;                      // STAR: the frame's non-blank log-sum-exp rides with lse
+    float cg[K][NG], cb[K], cl[K], cs[KS], ng[K][NG], nb[K], nl[K], ns[KS];
+    auto fetch = [&](int k0, float (&g)[K][NG], float (&gb)[K], float (&gl)[K], float (&gs)[KS]) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int kk = min(k0 + k, Tb - 1);
@@ -208,20 +227,27 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
             for (int g_ = 0; g_ < NG; ++g_) g[k][g_] = x[gsym[g_]];
             gb[k] = x[blank];
             gl[k] = lse[row];
+            if constexpr (STAR) gs[k] = lse_nb[row];
         }
     };
-    fetch(0, cg, cb, cl);
+    fetch(0, cg, cb, cl, cs);
     double *rows = (dir ? beta : alpha) + (size_t)b * T * srow;
     double *mrows = ENT ? (dir ? mbeta : malpha) + (size_t)b * T * srow : nullptr;
     for (int k0 = 0; k0 < Tb; k0 += K) {
-        fetch(k0 + K, ng, nb, nl);
+        fetch(k0 + K, ng, nb, nl, ns);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int kk = k0 + k;
             if (kk < Tb) {
                 const int t = dir ? Tb - 1 - kk : kk;
                 const float lz = cl[k];
-                const float eb = (cb[k] - lz) * LAT_LOG2E;
+                float eb = (cb[k] - lz) * LAT_LOG2E;
+                float esl = 0.0f;                                            // STAR: the star term of a label position
+                if constexpr (STAR) {
+                    const float nbl = (cs[k] - lz) * LAT_LOG2E;              // log2 of the frame's non-blank mass
+                    esl = nbl - star_b;
+                    eb = lat_star_mix(eb, nbl - star_s);
+                }
                 // DELAY, forward: the arcs into a label position of this row carry w(t).  Backward (reversed lattice): the arcs
                 // out of a label position of the row before, frame t + 1, carry w(t + 1) - that is p-1 -> p for an even p and
                 // p-2 -> p for an odd p.  An arc p-2 -> p joins two label positions in either direction.
@@ -258,12 +284,15 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
                         const double p2 = (allow2 & 1u) ? (DELAY ? in2 + w : in2) : NEG;
                         v = lat_lse3(a[0], DELAY ? p1 + ((lane & 1) ? w1odd : w1even) : p1, p2);
                         if (lane & 1) e = (cg[k][0] - lz) * LAT_LOG2E;
+                        if constexpr (STAR)
+                            if (lane & 1) e = lat_star_mix(e, esl);
                         live = live && t >= wlo[0] && t <= whi[0];           // blank lanes: lo = 0, hi = INT_MAX
                     } else if (j & 1) {
                         double p2 = j >= 2 ? a[j - 2] : in2;
                         p2 = (allow2 >> j & 1u) ? (DELAY ? p2 + w : p2) : NEG;
                         v = lat_lse3(a[j], DELAY ? p1 + w1odd : p1, p2);
                         e = (cg[k][g_] - lz) * LAT_LOG2E;
+                        if constexpr (STAR) e = lat_star_mix(e, esl);
                         live = live && t >= wlo[g_] && t <= whi[g_];
                     } else {
                         v = lat_lse2(a[j], DELAY ? p1 + w1even : p1);        // blanks are never entered from s-2
@@ -293,6 +322,7 @@ __global__ __launch_bounds__(64) void lat_sweep_kernel(const float *__restrict__
             for (int g_ = 0; g_ < NG; ++g_) cg[k][g_] = ng[k][g_];
             cb[k] = nb[k];
             cl[k] = nl[k];
+            if constexpr (STAR) cs[k] = ns[k];
         }
     }
     if (dir == 1) return;
@@ -357,7 +387,13 @@ __device__ __forceinline__ double lat_wave_sum_d(double x)
 // sum_s occupancy(t, s) * (Ebar - c(t, s)), c = malpha + mbeta - emission the mean log-probability of the paths through the
 // cell.  The plain part is summed exactly as without ENT (eta = 0 gives its bits); the products occupancy * (Ebar - c), each
 // formed as that product, are summed beside it in double in the same orders and the term is rounded once.
-template <bool ENTRY, bool ENT>
+// STAR (transcript-tolerant CTC; never with ENTRY or ENT): a cell's emission is the mixture e' = log2(2^e + 2^es), es the
+// star term of its parity.  The occupancies carry e' in the exponent; rho = 2^(e - e') and sigma = 2^(es - e') are the own
+// and the star share of the cell, each formed as that power (a dead side is 0 by a select, a cell with e' = -inf is never
+// visited).  grad = softmax - rho_k occ_k - [k < V-1] 2^((z_k - lse_nb) log2 e) M(t), M(t) = sum_k sigma_k occ_k in double
+// (each lane its classes in sequence, then the fixed butterfly), the last term in a second pass over the lane's own stores
+// and only where M(t) != 0.  M(t) goes to fterm; grad may be NULL, then nothing is stored and M(t) is the same sum.
+template <bool ENTRY, bool ENT, bool STAR>
 __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__ logits, int T, int B, int V,
                                                        const int *__restrict__ offs, const int *__restrict__ seq_len,
                                                        const float *__restrict__ lse, const double *__restrict__ alpha,
@@ -367,8 +403,10 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
                                                        const int *__restrict__ first, const int *__restrict__ cnt,
                                                        float *__restrict__ grad, double *__restrict__ fterm,
                                                        const double *__restrict__ malpha, const double *__restrict__ mbeta,
-                                                       const double *__restrict__ ebar, float eta)
+                                                       const double *__restrict__ ebar, float eta,
+                                                       const float *__restrict__ lse_nb, float star_b, float star_s)
 {
+    static_assert(!(STAR && (ENTRY || ENT)), "the star is built under neither the delay tilt nor the entropy term");
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= (size_t)T * B) return;
@@ -376,14 +414,17 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
     const int Tb = min(max(seq_len[b], 0), T);
     const int st = status[b];
     const float *x = logits + row * V;
-    float *g = grad + row * V;
+    const bool store = !STAR || grad != nullptr;                             // wave-uniform; only STAR runs without a gradient
+    float *g = store ? grad + row * V : nullptr;
     if (t >= Tb || st == LAT_ZERO || st == LAT_NAN) {                        // wave-uniform
-        for (int k = lane; k < V; k += 64) g[k] = 0.0f;
+        if (store)
+            for (int k = lane; k < V; k += 64) g[k] = 0.0f;
         return;
     }
     const float lz = lse[row];
     if (st == LAT_NOPATH) {
-        for (int k = lane; k < V; k += 64) g[k] = __builtin_amdgcn_exp2f((x[k] - lz) * LAT_LOG2E);
+        if (store)
+            for (int k = lane; k < V; k += 64) g[k] = __builtin_amdgcn_exp2f((x[k] - lz) * LAT_LOG2E);
         return;
     }
     const int L = offs[b + 1] - offs[b], S = 2 * L + 1;
@@ -394,13 +435,17 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
     double eacc = 0.0;                                                       // this lane's sum of occupancy * notyet
     const double *MA = ENT ? malpha + bt * srow : nullptr, *MB = ENT ? mbeta + bt * srow : nullptr;
     const double eb2 = ENT ? ebar[b] : 0.0, etal = ENT ? (double)eta * LAT_LN2 : 0.0;      // the means are in log2
+    const float lnb = STAR ? lse_nb[row] : 0.0f;
+    const float nbl = (lnb - lz) * LAT_LOG2E, esl = nbl - star_b, ess = nbl - star_s;      // STAR: the two star terms
+    double macc = 0.0;                                                       // STAR: this lane's sum of sigma_k * occ_k
     // the blank: positions 0, 2, .., 2L, lane l takes 2l, 2l + 128, ... in sequence, then the wave's fixed reduction
     const float eb = (x[blank] - lz) * LAT_LOG2E;
     {
-        const double c = (double)eb + lp;
+        const float em = STAR ? lat_star_mix(eb, ess) : eb;
+        const double c = (double)em + lp;
         float acc = 0.0f;
         double dacc = 0.0;                                                   // ENT: sum of occupancy * (Ebar - c)
-        for (int s = 2 * lane; s < S; s += 128) {
+        for (int s = 2 * lane; s < (STAR && !(em > -INFINITY) ? 0 : S); s += 128) {
             const float o = __builtin_amdgcn_exp2f((float)((A[s] + Bt[S - 1 - s]) - c));
             acc += o;
             if (ENTRY) eacc += (double)o * (double)(L - (s >> 1));
@@ -408,7 +453,14 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
         }
         acc = lc_wave_sum(acc);
         if (ENT) dacc = lat_wave_sum_d(dacc);
-        if (lane == 0) {
+        if constexpr (STAR) {
+            if (lane == 0) {
+                const float rho = eb > -INFINITY ? __builtin_amdgcn_exp2f(eb - em) : 0.0f;
+                const float sigma = ess > -INFINITY ? __builtin_amdgcn_exp2f(ess - em) : 0.0f;
+                macc = (double)sigma * (double)acc;
+                if (store) g[blank] = __builtin_amdgcn_exp2f(eb) - rho * acc;
+            }
+        } else if (lane == 0) {
             const float plain = __builtin_amdgcn_exp2f(eb) - acc;
             g[blank] = ENT ? plain - (float)(etal * dacc) : plain;
         }
@@ -418,8 +470,9 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
     const int *fr = first + (size_t)b * V, *cn = cnt + (size_t)b * V;
     for (int k = lane; k < blank; k += 64) {
         const float e = (x[k] - lz) * LAT_LOG2E;
-        const double c = (double)e + lp;
-        const int r0 = fr[k], n = cn[k];
+        const float em = STAR ? lat_star_mix(e, esl) : e;
+        const double c = (double)em + lp;
+        const int r0 = fr[k], n = STAR && !(em > -INFINITY) ? 0 : cn[k];
         float acc = 0.0f;
         double dacc = 0.0;
         for (int r = 0; r < n; ++r) {
@@ -429,8 +482,22 @@ __global__ __launch_bounds__(256) void lat_grad_kernel(const float *__restrict__
             if (ENTRY) eacc += (double)o * (double)(L - 1 - i);
             if (ENT) dacc += (double)o * (eb2 - ((MA[s] + MB[S - 1 - s]) - (double)e));
         }
-        const float plain = __builtin_amdgcn_exp2f(e) - acc;
-        g[k] = ENT ? plain - (float)(etal * dacc) : plain;
+        if constexpr (STAR) {
+            const float rho = e > -INFINITY ? __builtin_amdgcn_exp2f(e - em) : 0.0f;
+            const float sigma = esl > -INFINITY ? __builtin_amdgcn_exp2f(esl - em) : 0.0f;
+            macc += (double)sigma * (double)acc;
+            if (store) g[k] = __builtin_amdgcn_exp2f(e) - rho * acc;
+        } else {
+            const float plain = __builtin_amdgcn_exp2f(e) - acc;
+            g[k] = ENT ? plain - (float)(etal * dacc) : plain;
+        }
+    }
+    if constexpr (STAR) {
+        const double mt = lat_wave_sum_d(macc);                              // M(t), the same value in every lane
+        if (lane == 0) fterm[bt] = mt;
+        if (store && mt != 0.0)                                              // mt != 0 needs a live star term, so lnb > -inf
+            for (int k = lane; k < blank; k += 64)
+                g[k] -= (float)((double)__builtin_amdgcn_exp2f((x[k] - lnb) * LAT_LOG2E) * mt);
     }
     if (ENTRY) {
         eacc = lat_wave_sum_d(eacc);
@@ -490,12 +557,13 @@ __global__ __launch_bounds__(64) void lat_fold_kernel(const double *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------ host
-// the workspace: slabs in this order; only the delay entry has the frame terms, only the entropy entry Ebar and the means
+// the workspace: slabs in this order; only the delay and the star entry have the frame terms, only the entropy entry Ebar and
+// the means, only the star entry (last, so that it is the delay entry's layout plus one slab) the non-blank log-sum-exp
 struct LatLayout {
-    size_t lse, status, lp2, ebar, order, first, cnt, fterm, alpha, beta, malpha, mbeta, total;
+    size_t lse, status, lp2, ebar, order, first, cnt, fterm, alpha, beta, malpha, mbeta, lse_nb, total;
     int ppl, srow, pitch;
 };
-inline LatLayout lat_layout(int T, int B, int V, int max_label_len, bool with_fterm, bool with_means)
+inline LatLayout lat_layout(int T, int B, int V, int max_label_len, bool with_fterm, bool with_means, bool with_nb)
 {
     LatLayout m;
     const int S = 2 * max_label_len + 1;
@@ -516,45 +584,54 @@ inline LatLayout lat_layout(int T, int B, int V, int max_label_len, bool with_ft
     m.beta = o; o += lc_align256(TB * m.srow * sizeof(double));
     m.malpha = o; o += with_means ? lc_align256(TB * m.srow * sizeof(double)) : 0;
     m.mbeta = o; o += with_means ? lc_align256(TB * m.srow * sizeof(double)) : 0;
+    m.lse_nb = o; o += with_nb ? lc_align256(TB * sizeof(float)) : 0;
     m.total = o;
     return m;
 }
-inline size_t lat_workspace_bytes(int T, int B, int V, int max_label_len, bool with_fterm, bool with_means)
+inline size_t lat_workspace_bytes(int T, int B, int V, int max_label_len, bool with_fterm, bool with_means, bool with_nb)
 {
     if (T <= 0 || B <= 0 || V < 2 || max_label_len < 0 || max_label_len > 1023) return 0;
-    return lat_layout(T, B, V, max_label_len, with_fterm, with_means).total;
+    return lat_layout(T, B, V, max_label_len, with_fterm, with_means, with_nb).total;
 }
 
-// what tells the three entries apart on the host: the criterion, the names in front of an error, the tags of the launches
+// what tells the four entries apart on the host: the criterion, the names in front of an error, the tags of the launches
 struct LatEntry {
-    bool delay, entropy;
+    bool delay, entropy, star;
     const char *name, *weight, *lse, *index, *sweep, *grad, *entry, *fold;
 };
-const LatEntry LAT_WINDOW = {false, false, "lc_ctc_loss_windowed", "delay_penalty", "ctc_window_lse", "ctc_window_index",
+const LatEntry LAT_WINDOW = {false, false, false, "lc_ctc_loss_windowed", "delay_penalty", "ctc_window_lse", "ctc_window_index",
                              "ctc_window_sweep", "ctc_window_grad", "ctc_window_entry", "ctc_window_fold"};
-const LatEntry LAT_DELAY = {true, false, "lc_ctc_loss_delay", "delay_penalty", "ctc_delay_lse", "ctc_delay_index",
+const LatEntry LAT_DELAY = {true, false, false, "lc_ctc_loss_delay", "delay_penalty", "ctc_delay_lse", "ctc_delay_index",
                             "ctc_delay_sweep", "ctc_delay_grad", "ctc_delay_entry", "ctc_delay_fold"};
-const LatEntry LAT_ENTROPY = {false, true, "lc_ctc_loss_entropy", "entropy_weight", "ctc_entropy_lse", "ctc_entropy_index",
+const LatEntry LAT_ENTROPY = {false, true, false, "lc_ctc_loss_entropy", "entropy_weight", "ctc_entropy_lse", "ctc_entropy_index",
                               "ctc_entropy_sweep", "ctc_entropy_grad", "ctc_entropy_entry", "ctc_entropy_fold"};
+const LatEntry LAT_STAR = {false, false, true, "lc_ctc_loss_star", "bypass_penalty", "ctc_star_lse", "ctc_star_index",
+                           "ctc_star_sweep", "ctc_star_grad", "ctc_star_entry", "ctc_star_fold"};
 
-// ``weight`` is the delay penalty or the entropy weight, ``extra`` entry_sum [B] (delay; optional) or entropy [B] (entropy;
-// required).  The windowed entry comes with windows, weight 0 and no extra.
+// ``weight`` is the delay penalty, the entropy weight or the bypass penalty, ``weight2`` the star entry's self-loop penalty (0
+// otherwise), ``extra`` entry_sum [B] (delay; optional), entropy [B] (entropy; required) or star_frames [B] (star; required:
+// it is folded from the frame terms as entry_sum is).  The windowed entry comes with windows, weight 0 and no extra.
 int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
-               const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi, float weight, float *loss,
-               float *extra, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream)
+               const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi, float weight, float weight2,
+               float *loss, float *extra, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
     float *entry_sum = e.entropy ? nullptr : extra, *entropy = e.entropy ? extra : nullptr;
-    LC_CHECK_ARG(logits && labels && label_offsets && seq_len && loss && workspace && (!e.entropy || entropy) &&
-                     (e.delay || e.entropy || (win_lo && win_hi)),
+    LC_CHECK_ARG(logits && labels && label_offsets && seq_len && loss && workspace && (!(e.entropy || e.star) || extra) &&
+                     (e.delay || e.entropy || e.star || (win_lo && win_hi)),
                  "%s: null pointer", e.name);
     LC_CHECK_ARG((win_lo == nullptr) == (win_hi == nullptr), "%s: win_lo and win_hi go together (both or none)", e.name);
     LC_CHECK_ARG(T > 0 && B > 0 && V >= 2 && max_label_len >= 0, "%s: bad shape T=%d B=%d V=%d L=%d", e.name, T, B, V,
                  max_label_len);
     LC_CHECK_ARG(max_label_len <= 1023, "%s: label length %d exceeds the supported maximum 1023", e.name, max_label_len);
-    LC_CHECK_ARG(isfinite(weight), "%s: %s must be finite, got %g", e.name, e.weight, (double)weight);
+    if (e.star) {                                        // +inf is legal: it switches that arc family off
+        LC_CHECK_ARG(weight >= 0.0f, "%s: bypass_penalty must be >= 0 or +inf, got %g", e.name, (double)weight);
+        LC_CHECK_ARG(weight2 >= 0.0f, "%s: selfloop_penalty must be >= 0 or +inf, got %g", e.name, (double)weight2);
+    } else {
+        LC_CHECK_ARG(isfinite(weight), "%s: %s must be finite, got %g", e.name, e.weight, (double)weight);
+    }
     LC_CHECK_ARG((long long)B * 2 <= 0x7fffffffLL && ((long long)T * B + 3) / 4 <= 0x7fffffffLL,
                  "%s: T * B = %lld is beyond the launch grid", e.name, (long long)T * B);
-    const LatLayout m = lat_layout(T, B, V, max_label_len, e.delay, e.entropy);
+    const LatLayout m = lat_layout(T, B, V, max_label_len, e.delay || e.star, e.entropy, e.star);
     if (workspace_bytes < m.total) {
         lc_set_error("%s: workspace too small (%zu < %zu)", e.name, workspace_bytes, m.total);
         return LC_EWORKSPACE;
@@ -568,52 +645,71 @@ int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, cons
     double *fterm = (double *)(w + m.fterm);             // only with entry_sum, which only the delay entry has
     double *alpha = (double *)(w + m.alpha), *beta = (double *)(w + m.beta);
     double *ebar = (double *)(w + m.ebar), *malpha = (double *)(w + m.malpha), *mbeta = (double *)(w + m.mbeta);   // entropy only
+    float *lse_nb = (float *)(w + m.lse_nb);              // star only
+    // star: log2(V - 1) + penalty * log2(e), formed in double and rounded once; +inf with the penalty
+    const float star_b = e.star ? (float)(log2((double)(V - 1)) + (double)weight * LAT_LOG2E_D) : 0.0f;
+    const float star_s = e.star ? (float)(log2((double)(V - 1)) + (double)weight2 * LAT_LOG2E_D) : 0.0f;
     const unsigned frame_blocks = (unsigned)(((long long)T * B + 3) / 4);
-    hipLaunchKernelGGL(lat_lse_kernel, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, seq_len, lse);
+    if (e.star)
+        hipLaunchKernelGGL(lat_lse_kernel<true>, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, seq_len, lse, lse_nb);
+    else
+        hipLaunchKernelGGL(lat_lse_kernel<false>, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, seq_len, lse,
+                           (float *)nullptr);
     LC_CHECK_LAUNCH(e.lse);
-    if (grad) {
+    if (grad || e.star) {                                // the star's frame terms are summed in the gradient's order
         hipLaunchKernelGGL(lat_index_kernel, dim3(B), dim3(256), 0, s, V, labels, label_offsets, max_label_len, m.pitch, order,
                            first, cnt);
         LC_CHECK_LAUNCH(e.index);
     }
-#define LC_LAT(PPL, DELAY, ENT)                                                                                         \
-    hipLaunchKernelGGL((lat_sweep_kernel<PPL, DELAY, ENT>), dim3(2 * B), dim3(64), 0, s, logits, T, B, V, labels,       \
+#define LC_LAT(PPL, DELAY, ENT, STAR)                                                                                   \
+    hipLaunchKernelGGL((lat_sweep_kernel<PPL, DELAY, ENT, STAR>), dim3(2 * B), dim3(64), 0, s, logits, T, B, V, labels, \
                        label_offsets, seq_len, max_label_len, win_lo, win_hi, weight, lse, alpha, beta, m.srow,         \
-                       (grad || entry_sum) ? 1 : 0, loss, lp2, status, malpha, mbeta, ebar, entropy)
-    switch (e.delay ? -m.ppl : e.entropy ? 64 + m.ppl : m.ppl) {         // the sign picks the DELAY instantiations, + 64 ENT
-    case 1: LC_LAT(1, false, false); break;
-    case 2: LC_LAT(2, false, false); break;
-    case 4: LC_LAT(4, false, false); break;
-    case 8: LC_LAT(8, false, false); break;
-    case 16: LC_LAT(16, false, false); break;
-    case 32: LC_LAT(32, false, false); break;
-    case 65: LC_LAT(1, false, true); break;
-    case 66: LC_LAT(2, false, true); break;
-    case 68: LC_LAT(4, false, true); break;
-    case 72: LC_LAT(8, false, true); break;
-    case 80: LC_LAT(16, false, true); break;
-    case 96: LC_LAT(32, false, true); break;
-    case -1: LC_LAT(1, true, false); break;
-    case -2: LC_LAT(2, true, false); break;
-    case -4: LC_LAT(4, true, false); break;
-    case -8: LC_LAT(8, true, false); break;
-    case -16: LC_LAT(16, true, false); break;
-    default: LC_LAT(32, true, false); break;
+                       (grad || entry_sum) ? 1 : 0, loss, lp2, status, malpha, mbeta, ebar, entropy, lse_nb, star_b,    \
+                       star_s)
+    // the sign picks the DELAY instantiations, + 64 ENT, + 128 STAR
+    switch (e.delay ? -m.ppl : e.entropy ? 64 + m.ppl : e.star ? 128 + m.ppl : m.ppl) {
+    case 1: LC_LAT(1, false, false, false); break;
+    case 2: LC_LAT(2, false, false, false); break;
+    case 4: LC_LAT(4, false, false, false); break;
+    case 8: LC_LAT(8, false, false, false); break;
+    case 16: LC_LAT(16, false, false, false); break;
+    case 32: LC_LAT(32, false, false, false); break;
+    case 65: LC_LAT(1, false, true, false); break;
+    case 66: LC_LAT(2, false, true, false); break;
+    case 68: LC_LAT(4, false, true, false); break;
+    case 72: LC_LAT(8, false, true, false); break;
+    case 80: LC_LAT(16, false, true, false); break;
+    case 96: LC_LAT(32, false, true, false); break;
+    case 129: LC_LAT(1, false, false, true); break;
+    case 130: LC_LAT(2, false, false, true); break;
+    case 132: LC_LAT(4, false, false, true); break;
+    case 136: LC_LAT(8, false, false, true); break;
+    case 144: LC_LAT(16, false, false, true); break;
+    case 160: LC_LAT(32, false, false, true); break;
+    case -1: LC_LAT(1, true, false, false); break;
+    case -2: LC_LAT(2, true, false, false); break;
+    case -4: LC_LAT(4, true, false, false); break;
+    case -8: LC_LAT(8, true, false, false); break;
+    case -16: LC_LAT(16, true, false, false); break;
+    default: LC_LAT(32, true, false, false); break;
     }
 #undef LC_LAT
     LC_CHECK_LAUNCH(e.sweep);
-#define LC_LAT_GRAD(ENTRY, ENT)                                                                                         \
-    hipLaunchKernelGGL((lat_grad_kernel<ENTRY, ENT>), dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, label_offsets, \
-                       seq_len, lse, alpha, beta, m.srow, lp2, status, order, m.pitch, first, cnt, grad, fterm, malpha,  \
-                       mbeta, ebar, weight)
-    if (grad && entropy) {
-        LC_LAT_GRAD(false, true);
+#define LC_LAT_GRAD(ENTRY, ENT, STAR)                                                                                   \
+    hipLaunchKernelGGL((lat_grad_kernel<ENTRY, ENT, STAR>), dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V,       \
+                       label_offsets, seq_len, lse, alpha, beta, m.srow, lp2, status, order, m.pitch, first, cnt, grad, \
+                       fterm, malpha, mbeta, ebar, weight, lse_nb, star_b, star_s)
+    if (e.star) {                                        // also without a gradient: the same pass, storing only M(t)
+        LC_LAT_GRAD(false, false, true);
+        LC_CHECK_LAUNCH(e.grad);
+    } else if (grad && entropy) {
+        LC_LAT_GRAD(false, true, false);
         LC_CHECK_LAUNCH(e.grad);
     } else if (grad && entry_sum) {
-        LC_LAT_GRAD(true, false);
+        LC_LAT_GRAD(true, false, false);
         LC_CHECK_LAUNCH(e.grad);
     } else if (grad) {
-        LC_LAT_GRAD(false, false);
+        LC_LAT_GRAD(false, false, false);
         LC_CHECK_LAUNCH(e.grad);
     } else if (entry_sum) {
         hipLaunchKernelGGL(lat_entry_kernel, dim3(frame_blocks), dim3(256), 0, s, logits, T, B, V, labels, label_offsets,
@@ -632,17 +728,31 @@ int lat_launch(const LatEntry &e, const float *logits, int T, int B, int V, cons
 
 extern "C" size_t lc_ctc_window_workspace_bytes(int T, int B, int V, int max_label_len)
 {
-    return lat_workspace_bytes(T, B, V, max_label_len, false, false);
+    return lat_workspace_bytes(T, B, V, max_label_len, false, false, false);
 }
 
 extern "C" size_t lc_ctc_delay_workspace_bytes(int T, int B, int V, int max_label_len)
 {
-    return lat_workspace_bytes(T, B, V, max_label_len, true, false);
+    return lat_workspace_bytes(T, B, V, max_label_len, true, false, false);
 }
 
 extern "C" size_t lc_ctc_entropy_workspace_bytes(int T, int B, int V, int max_label_len)
 {
-    return lat_workspace_bytes(T, B, V, max_label_len, false, true);
+    return lat_workspace_bytes(T, B, V, max_label_len, false, true, false);
+}
+
+extern "C" size_t lc_ctc_star_workspace_bytes(int T, int B, int V, int max_label_len)
+{
+    return lat_workspace_bytes(T, B, V, max_label_len, true, false, true);
+}
+
+extern "C" int lc_ctc_loss_star(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
+                                const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
+                                float bypass_penalty, float selfloop_penalty, float *loss, float *star_frames, float *grad,
+                                void *workspace, size_t workspace_bytes, lc_stream_t stream)
+{
+    return lat_launch(LAT_STAR, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi,
+                      bypass_penalty, selfloop_penalty, loss, star_frames, grad, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lc_ctc_loss_entropy(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
@@ -651,14 +761,14 @@ extern "C" int lc_ctc_loss_entropy(const float *logits, int T, int B, int V, con
                                    size_t workspace_bytes, lc_stream_t stream)
 {
     return lat_launch(LAT_ENTROPY, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi,
-                      entropy_weight, loss, entropy, grad, workspace, workspace_bytes, stream);
+                      entropy_weight, 0.0f, loss, entropy, grad, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lc_ctc_loss_windowed(const float *logits, int T, int B, int V, const int *labels, const int *label_offsets,
                                     const int *seq_len, int max_label_len, const int *win_lo, const int *win_hi,
                                     float *loss, float *grad, void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    return lat_launch(LAT_WINDOW, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi, 0.0f, loss,
+    return lat_launch(LAT_WINDOW, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi, 0.0f, 0.0f, loss,
                       nullptr, grad, workspace, workspace_bytes, stream);
 }
 
@@ -668,5 +778,5 @@ extern "C" int lc_ctc_loss_delay(const float *logits, int T, int B, int V, const
                                  size_t workspace_bytes, lc_stream_t stream)
 {
     return lat_launch(LAT_DELAY, logits, T, B, V, labels, label_offsets, seq_len, max_label_len, win_lo, win_hi, delay_penalty,
-                      loss, entry_sum, grad, workspace, workspace_bytes, stream);
+                      0.0f, loss, entry_sum, grad, workspace, workspace_bytes, stream);
 }

@@ -181,6 +181,18 @@ class _HostScalars:
         return dict(zip(self.names, torch.cat(self.parts).cpu().tolist()))
 
 
+def _checked_star_penalty(value):
+    """``star_penalty`` as a pair of floats (bypass, self-loop), each a number - never a bool - that is >= 0 or +inf; else
+    ValueError naming the keyword."""
+    must_be = "a pair (bypass_penalty, selfloop_penalty) of floats >= 0 or +inf, or None"
+    if not isinstance(value, (tuple, list)) or len(value) != 2:
+        raise ValueError("star_penalty must be %s, got %r" % (must_be, value))
+    for p in value:
+        if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not p >= 0:
+            raise ValueError("star_penalty must be %s, got %r" % (must_be, value))
+    return float(value[0]), float(value[1])
+
+
 def _checked_number(name, value, lower, strict, must_be, integer=False):
     """``value`` as a float (``integer``: an int) when it is a finite number - never a bool - that is > ``lower`` (``strict``)
     or >= it; else ValueError("<name> must be <must_be>, got <value>")."""
@@ -233,6 +245,17 @@ class CTCGraph:
     own).  0 is plain CTC plus the metric.  It does not combine with ``delay_penalty`` (the entropy of the tilted posterior
     is not built).  ``None`` is the step without it, untouched.
 
+    ``star_penalty=(pb, ps)`` (new, ``objective="ctc"`` only; each a float >= 0 or +inf) is transcript-tolerant CTC (after
+    OTC / STC): every lattice position may explain a frame by a penalised star, "some non-blank class", instead of by its own
+    class - a label position at ``exp(-pb)`` (the label is bypassed: a substituted or inserted label), a blank position at
+    ``exp(-ps)`` (the blank absorbs speech: a deleted label) - so that wrong transcripts neither blow the loss up nor push
+    correctly recognised frames towards the wrong label (``ops.ctc_loss_star`` where the step calls ``ops.ctc_loss`` /
+    ``ops.ctc_loss_windowed``; with ``align_window`` the windows go to it).  ``eval_loss`` / ``loss`` are that criterion (it
+    may be negative); the output gains ``star_frames`` (the float64 sum over the utterances with a finite, non-skipped loss of
+    the expected number of frames the star explains) and ``star_frame_count`` (the sum of their sequence lengths);
+    ``star_frames_total`` / ``star_frame_count_total`` sum over the steps (each rank its own).  It combines with neither
+    ``delay_penalty`` nor ``entropy_weight``.  ``None`` is the step without it, untouched.
+
     ``spec_augment=SpecAugment(...)`` (new, training graphs, every objective; ``nnet.augment``) masks the input of every
     TRAINING step on the device: the model reads ``ops.spec_augment(x, ...)``, written OUT OF PLACE - the caller's ``x`` is
     never changed, so ``step_device`` callers may pass the same tensor step after step.  The draws are seeded with the step's
@@ -263,7 +286,7 @@ class CTCGraph:
     def __init__(self, pipeline, nnet_config, learn_rate=None, clip_norm=5.0, optimizer="sgd",
                  l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, objective="ctc", align_window=None,
                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None,
-                 consistency_weight=None, entropy_weight=None):
+                 consistency_weight=None, entropy_weight=None, star_penalty=None):
         nnet_type = nnet_config.get("nnet_type")
         if get_create_logits(nnet_type) is None:
             raise ValueError("unsupported nnet_type: %s" % nnet_type)
@@ -300,6 +323,16 @@ class CTCGraph:
                                  "posterior is not built)")
         self.entropy_weight = entropy_weight
         self.path_entropy_total, self.path_entropy_frames_total = 0.0, 0
+        if star_penalty is not None:
+            if objective != "ctc":
+                raise ValueError("star_penalty relaxes the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
+            star_penalty = _checked_star_penalty(star_penalty)
+            if delay_penalty is not None:
+                raise ValueError("star_penalty does not combine with delay_penalty (the star under the delay tilt is not built)")
+            if entropy_weight is not None:
+                raise ValueError("star_penalty does not combine with entropy_weight (the star under the entropy term is not built)")
+        self.star_penalty = star_penalty
+        self.star_frames_total, self.star_frame_count_total = 0.0, 0
         self.spec_layout = None
         if spec_augment is not None:
             from . import augment
@@ -599,7 +632,7 @@ class CTCGraph:
     # host, reduced at the step's one copy; ``outputs(host, out, fetch_eval)`` writing size, eval_loss, eval and its own keys
     # into ``out`` from the fetched {name: float} - and adding to its ``*_total`` counters, so only for a step that completed.
     def _ctc_criterion(self, logits, b, train):
-        entry_b = entropy_b = None
+        entry_b = entropy_b = star_b = None
         if self.delay_penalty is not None:
             lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
             loss_b, entry_b, grad = ops.ctc_loss_delay(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.delay_penalty,
@@ -608,6 +641,10 @@ class CTCGraph:
             lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
             loss_b, entropy_b, grad = ops.ctc_loss_entropy(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.entropy_weight,
                                                            win_lo=lo_d, win_hi=hi_d, want_grad=train)
+        elif self.star_penalty is not None:
+            lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
+            loss_b, star_b, grad = ops.ctc_loss_star(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.star_penalty[0],
+                                                     self.star_penalty[1], win_lo=lo_d, win_hi=hi_d, want_grad=train)
         elif self.align_window is not None:
             loss_b, grad = ops.ctc_loss_windowed(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, b.windows[0], b.windows[1],
                                                  want_grad=train)
@@ -622,6 +659,8 @@ class CTCGraph:
             pairs = [("eval_loss", loss_b.sum())]                                # graph.py:116 reduce_sum, in float32
             if entry_b is not None:
                 pairs += zip(("entry_sum", "entry_labels"), self._entry_scalars(loss_b, entry_b, b.offs_d, b.seq_d))
+            if star_b is not None:                                               # the same selection and sums as the entropy's
+                pairs += zip(("star_frames", "star_frame_count"), self._entropy_scalars(loss_b, star_b, b.offs_d, b.seq_d))
             return pairs
 
         def outputs(host, out, fetch_eval):                  # (``eval`` needs the greedy decode: the tail's)
@@ -634,6 +673,10 @@ class CTCGraph:
                 out["path_entropy"], out["path_entropy_frames"] = host["path_entropy"], int(host["path_entropy_frames"])
                 self.path_entropy_total += out["path_entropy"]
                 self.path_entropy_frames_total += out["path_entropy_frames"]
+            if star_b is not None:
+                out["star_frames"], out["star_frame_count"] = host["star_frames"], int(host["star_frame_count"])
+                self.star_frames_total += out["star_frames"]
+                self.star_frame_count_total += out["star_frame_count"]
         return grad, scalars, outputs
 
     def _xent_criterion(self, logits, b, train):
@@ -676,7 +719,8 @@ class CTCGraph:
 
     @staticmethod
     def _entropy_scalars(loss_b, entropy_b, offs_d, seq_d):
-        """entropy_weight: [sum of entropy, sum of seq_len] over the utterances with a finite, non-skipped loss."""
+        """entropy_weight (and star_penalty, with star_frames as ``entropy_b``): [sum of entropy, sum of seq_len] over the
+        utterances with a finite, non-skipped loss."""
         n = (offs_d[1:] - offs_d[:-1]).to(torch.int64)
         ok = torch.isfinite(loss_b) & (seq_d > 0) & (n <= seq_d)
         zero = torch.zeros((), dtype=torch.float64, device=loss_b.device)
@@ -768,12 +812,17 @@ class CTCGraph:
         return out, 0
 
     # ------------------------------------------------------------------------------------------------- forced alignment
-    def align(self, batch):
+    def align(self, batch, star_penalty=None):
         """Best-path (Viterbi) CTC alignment of one batch in the pipeline contract - no reference counterpart.  One forward
         in inference mode (no dropout, batch-norm on its moving averages), then ``ops.ctc_align`` on the logits.  Returns
         host arrays: ``ali`` [B,T] int32 (symbol per frame, blank = V-1; -1 beyond an utterance's length and when its labels
         do not fit its frames), ``label_index`` [B,T] int32, ``score`` [B] float32 (-inf without a path) and
-        ``sequence_length``.  Never trains: parameters, ``global_step`` and the dropout stream are left as they were."""
+        ``sequence_length``.  Never trains: parameters, ``global_step`` and the dropout stream are left as they were.
+        ``star_penalty=(pb, ps)`` (new) adds ``ctc_loss``, ``star_loss`` and ``star_frames``, each [B] float32: ``ops.ctc_loss``
+        and ``ops.ctc_loss_star`` on the same logits, no gradient - what a per-utterance transcript report is written from;
+        ``ali``, ``label_index`` and ``score`` are what they are without it."""
+        if star_penalty is not None:
+            star_penalty = _checked_star_penalty(star_penalty)
         x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = self._upload(batch)
         self._validate_labels(flat)
         model, dev = self.model, self.model.device
@@ -784,13 +833,20 @@ class CTCGraph:
                 ops.lstm_status(dev).zero_()
                 logits = model.forward(x, seq_d, seq_len_host=seq)
                 res = ops.ctc_align(logits, flat_d, offs_d, seq_d, maxlen)
+                if star_penalty is not None:
+                    plain, _ = ops.ctc_loss(logits, flat_d, offs_d, seq_d, maxlen, want_grad=False)
+                    star_loss, star_frames, _ = ops.ctc_loss_star(logits, flat_d, offs_d, seq_d, maxlen, star_penalty[0],
+                                                                  star_penalty[1], want_grad=False)
+                    res = tuple(res) + (plain, star_loss, star_frames)
                 return res, int(ops.lstm_status(dev).item())
 
-            ali, lidx, score = self._fallback.run(run)
+            res = self._fallback.run(run)
         finally:
             model.is_training, model.keep = mode
-        return {"ali": ali.cpu().numpy(), "label_index": lidx.cpu().numpy(), "score": score.cpu().numpy(),
-                "sequence_length": seq}
+        names = ("ali", "label_index", "score", "ctc_loss", "star_loss", "star_frames")
+        out = {k: v.cpu().numpy() for k, v in zip(names, res)}
+        out["sequence_length"] = seq
+        return out
 
     def _apply_gradients(self):
         """L2 + clip_by_global_norm + optimizer.apply_gradients (graph.py:183-200), after the DP all-reduce.  The
@@ -888,21 +944,22 @@ def load_params(ps, path):
 
 # ----------------------------------------------------------------------------------------------------- reference-named factories
 def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None, align_window=None,
-                                    teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, entropy_weight=None):
+                                    teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, entropy_weight=None,
+                                    star_penalty=None):
     return CTCGraph(pipeline, nnet_config, device=device, seed=seed, align_window=align_window,
                     teacher_weight=teacher_weight, teacher_temperature=teacher_temperature, delay_penalty=delay_penalty,
-                    entropy_weight=entropy_weight)
+                    entropy_weight=entropy_weight, star_penalty=star_penalty)
 
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None,
                                   teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None,
-                                  consistency_weight=None, entropy_weight=None):
+                                  consistency_weight=None, entropy_weight=None, star_penalty=None):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
                     align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature,
                     delay_penalty=delay_penalty, spec_augment=spec_augment, consistency_weight=consistency_weight,
-                    entropy_weight=entropy_weight)
+                    entropy_weight=entropy_weight, star_penalty=star_penalty)
 
 
 def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None, teacher_weight=None,

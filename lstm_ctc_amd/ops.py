@@ -396,6 +396,47 @@ def ctc_loss_entropy(logits, labels, offsets, seq_len, max_label_len, entropy_we
     return loss, entropy, grad
 
 
+def ctc_loss_star(logits, labels, offsets, seq_len, max_label_len, bypass_penalty, selfloop_penalty, win_lo=None, win_hi=None,
+                  want_grad=True):
+    """Transcript-tolerant CTC (after OTC / STC) - no reference counterpart.  Arguments as for :func:`ctc_loss`, plus the two
+    penalties (each a float >= 0 or +inf, which switches that star off) and, optionally, the windows of
+    :func:`ctc_loss_windowed` (both or none).  Returns (loss[B], star_frames[B], grad[T,B,V] or None): loss is -log of the path
+    sum over the lattice whose cells may explain a frame by the penalised star (it may be negative), star_frames the expected
+    number of frames the star explains under the path posterior, grad the exact gradient of loss."""
+    lib = _lib.load()
+    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
+    logits = _f32c(logits)
+    T, B, V = logits.shape
+    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
+    for name, p in (("bypass_penalty", bypass_penalty), ("selfloop_penalty", selfloop_penalty)):
+        if isinstance(p, bool) or not p >= 0:                                   # NaN fails the comparison
+            raise ValueError("ctc_loss_star: %s must be a float >= 0 or +inf, got %r" % (name, p))
+    if (win_lo is None) != (win_hi is None):
+        raise ValueError("ctc_loss_star: win_lo and win_hi go together (both or none)")
+    if win_lo is not None:
+        assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
+        if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
+            raise ValueError("ctc_loss_star: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
+                             % (win_lo.numel(), win_hi.numel(), labels.numel()))
+        win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    star = torch.empty(B, dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits) if want_grad else None
+    nbytes = lib.lc_ctc_star_workspace_bytes(T, B, V, int(max_label_len))
+    ws = workspace("ctc_star", nbytes, logits.device)
+    if labels.numel() == 0:
+        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
+        if win_lo is not None:
+            win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
+            win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    ev = _prof_begin()
+    _lib.check(lib.lc_ctc_loss_star(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len),
+                                    _ptr(win_lo), _ptr(win_hi), float(bypass_penalty), float(selfloop_penalty), _ptr(loss),
+                                    _ptr(star), _ptr(grad), _ptr(ws), nbytes, _stream()), "lc_ctc_loss_star")
+    _prof_end("ctc", (T, B, V), ev)
+    return loss, star, grad
+
+
 WINDOW_OPEN = np.iinfo(np.int32).max
 
 
