@@ -359,6 +359,20 @@ def report_chunking(nnet_config):
         tflog.info(line)
 
 
+def report_row_conv(nnet_config):
+    """One INFO line when <nnet-config> sets row_conv_frames (the uni-LSTM's row convolution): tau and how far
+    past their own frame the logits read, in model frames and in raw frames (x subsample, + right_context).  A config the
+    model refuses: the FATAL line and exit 1, before a model is built."""
+    from lstm_ctc_amd.nnet.model import row_conv_info_line
+    try:
+        line = row_conv_info_line(nnet_config)
+    except ValueError as exc:
+        _fatal(str(exc))
+    if line:
+        from lstm_ctc_amd.nnet import tflog
+        tflog.info(line)
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:

@@ -7,7 +7,7 @@ import sys
 from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
                      report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, delay_keywords,
                      report_delay_penalty, spec_augment_keywords, report_spec_augment, consistency_keywords, report_consistency,
-                     report_chunking, entropy_keywords, report_entropy_weight, star_keywords, report_star_penalty)
+                     report_chunking, report_row_conv, entropy_keywords, report_entropy_weight, star_keywords, report_star_penalty)
 
 
 def main(args):
@@ -26,6 +26,7 @@ def main(args):
         nnet_config = nnet.parse_config(args.nnet_config)
         nnet_config['is_training'] = True
         report_chunking(nnet_config)                      # chunk_frames / lookahead_frames: one INFO line
+        report_row_conv(nnet_config)                      # row_conv_frames: one INFO line
         nnet_type = nnet_config.get('nnet_type')
         filename, tfrecord, input_dim = nnet.dataset_from_tfrecords(
             tfrecords_scp=args.tfrecords_scp, left_context=nnet_config.get('left_context'),

@@ -653,6 +653,38 @@ int lc_chunk_gather(const float *x, int ldx, int T, int B, int C, int chunk, int
 int lc_chunk_fold(const float *xc, int ldc, int T, int B, int C, int chunk, int lookahead, int sum_copies,
                   const int *seq_len /* or NULL */, float *out, int ldo, lc_stream_t stream);
 
+/* ------------------------------------------------------------------ row convolution --------- */
+/* Row convolution (lookahead convolution; Amodei et al. 2016, "Deep Speech 2"; no reference counterpart): one
+ * depthwise filter over the next tau frames of the uni-LSTM's top layer, tau frames of lookahead for (tau + 1) * C parameters.
+ * x, y, dy, dx are time-major [T * B, C] with row pitches ldx / ldy / lddy / lddx in floats (column windows of wider buffers
+ * are fine); w and dw are dense [tau + 1, C]; seq_len is a device [B] int32 and is REQUIRED.  With
+ * len_b = clamp(seq_len[b], 0, T) and live(t, b) = t < len_b:
+ *   lc_row_conv_fwd   y[t, b, c]  = sum over j = 0 .. tau with live(t + j, b) of w[j, c] * x[t + j, b, c]   if live(t, b), else +0
+ *   lc_row_conv_bwd   dx[t, b, c] = sum over j = 0 .. min(tau, t) of w[j, c] * dy[t - j, b, c]               if live(t, b), else +0
+ *                     dw[j, c]    = sum over b and over t with live(t + j, b) of dy[t, b, c] * x[t + j, b, c]  (overwritten, not
+ *                                   accumulated)
+ *   - Dead rows are never read: a frame at or past len_b contributes nothing whatever it holds (NaN included), so the result
+ *     does not depend on the padding or on what else is in the batch.
+ *   - Full writes: every element of y, dx and dw is written on every successful call (no memset needed), and nothing outside
+ *     the [T * B, C] windows (the [tau + 1, C] block of dw) is touched.
+ *   - Summation order of y and dx: ascending j, the first term initialising the sum (no 0 + ...); FMA contraction is allowed.
+ *     A kernel that is 1 in row j0 and 0 elsewhere therefore copies finite inputs exactly.
+ *   - Determinism: no atomics.  dw sums row slabs into the workspace and folds them in a fixed order, like lc_colsum; its
+ *     summation order is otherwise unspecified.  The same call gives the same bits.
+ *   - Pointers: dx or dw may be NULL, not both; x may be NULL when dw is.  x and y must not overlap, nor dx and dy (equal
+ *     pointers included); two disjoint column windows of one buffer do not overlap.
+ *   - Elements are indexed in 64 bits.  16-byte accesses when C and the pitches are multiples of 4 and the bases (w and the
+ *     workspace included) 16-byte aligned, a scalar path otherwise.
+ * LC_EINVAL, with nothing launched and no output touched: T, B, C <= 0; tau < 0 or tau > 32 (a design cap: the weights of a
+ * column group live in LDS); a NULL required pointer; a pitch below C; the overlaps above.  LC_EWORKSPACE, likewise: a non-NULL
+ * dw with a workspace below lc_row_conv_workspace_bytes (0 for a bad shape). */
+size_t lc_row_conv_workspace_bytes(int T, int B, int C, int tau);
+int lc_row_conv_fwd(const float *x, int ldx, const float *w, int T, int B, int C, int tau, const int *seq_len, float *y, int ldy,
+                    lc_stream_t stream);
+int lc_row_conv_bwd(const float *x, int ldx, const float *dy, int lddy, const float *w, int T, int B, int C, int tau,
+                    const int *seq_len, float *dx /* or NULL */, int lddx, float *dw /* or NULL */, void *workspace,
+                    size_t workspace_bytes, lc_stream_t stream);
+
 /* ------------------------------------------------------------------ SpecAugment ------------- */
 /* Time and frequency masking of the filterbank input (Park et al., 2019; no reference counterpart), on the spliced and
  * subsampled batch the loader uploads.  x and out are time-major [T * B, D] with row pitches ldx / ldo (floats); out == x (in

@@ -87,6 +87,10 @@ SIGNATURES = {
     "lc_unpack_rows": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "lc_chunk_gather": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "lc_chunk_fold": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lc_row_conv_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "lc_row_conv_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lc_row_conv_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lc_spec_augment": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_u32, c_void_p, c_int, c_void_p,
                                 c_void_p]),
     "lc_lstm_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -96,6 +96,12 @@ class ParamStore:
             self.aux_specs += [(bn + "/moving_mean", (C,), 0.0), (bn + "/moving_variance", (C,), 1.0)]
         H = (2 if self.blstm else 1) * self.Pout
         self.H = H
+        # row convolution (extension key row_conv_frames): one [tau + 1, H] filter between the top layer (its
+        # batch norm) and the head - behind the layers' tensors, so that layer_grad_range and the data-parallel buckets keep
+        # their ranges; no "bias" in the name: L2-decayed like every other kernel
+        self.row_conv = row_conv_config(cfg)
+        if self.row_conv:
+            specs.append(("row_conv/kernel", (self.row_conv + 1, H), "row_conv"))
         if self.E > 0:                                                            # moe.py:33-58
             specs += [("Variable", (H, self.E), "head_w"), ("Variable_1", (self.E,), "head_b"),
                       ("Variable_2", (H, self.E * V), "head_w"), ("Variable_3", (self.E * V,), "head_b")]
@@ -160,6 +166,14 @@ class ParamStore:
     def load_tf(self, params):
         """params: dict name -> numpy array in TF layout (tf.trainable_variables shapes)."""
         missing = [n for n in self.names() if n not in params]
+        if missing == ["row_conv/kernel"]:
+            # a plain model's checkpoint: the identity filter computes what that model computed (fine-tuning with lookahead)
+            from . import tflog
+            tflog.info("checkpoint has no row_conv/kernel: row convolution starts from the identity (row 0 ones, %d rows of "
+                       "zeros)" % self.row_conv)
+            params = dict(params)
+            params["row_conv/kernel"] = row_conv_identity(self.shapes["row_conv/kernel"])
+            missing = []
         if missing:
             raise KeyError("checkpoint lacks variables: %s" % missing)
         for name in self.names():
@@ -210,6 +224,8 @@ class ParamStore:
                 params[name] = a.astype(np.float32)
             elif kind == "bn_gamma":
                 params[name] = np.ones(shape, np.float32)
+            elif kind == "row_conv":
+                params[name] = row_conv_identity(shape)            # nothing drawn: the other tensors are the plain model's
             else:
                 params[name] = np.zeros(shape, np.float32)
         self.load_tf(params)
@@ -284,6 +300,50 @@ def chunk_config(cfg):
     return Nc, Nr
 
 
+ROW_CONV_MAX_FRAMES = 32      # the library's cap (lc_row_conv_fwd: a column group's weights live in LDS)
+
+
+def row_conv_config(cfg):
+    """tau of the row-convolution key ``row_conv_frames`` (extension, model frames), validated: 0 when the key
+    is absent or 0 - today's model -, else an integer in 1..32 and a unidirectional nnet_type.  Like the chunk keys it changes
+    what the model computes, so what cannot run it is refused here."""
+    v = cfg.get("row_conv_frames")
+    if v is None:
+        return 0
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > ROW_CONV_MAX_FRAMES:
+        raise ValueError("row_conv_frames must be an integer in 0..%d (model frames), got %r" % (ROW_CONV_MAX_FRAMES, v))
+    if v == 0:
+        return 0
+    if cfg.get("nnet_type", "blstm") == "blstm":
+        raise ValueError("row_conv_frames gives a unidirectional model (nnet_type = lstm or cudnnlstm) lookahead; nnet_type = "
+                         "blstm already reads the whole future")
+    return int(v)
+
+
+def row_conv_identity(shape):
+    """The filter that leaves the model as it was: row 0 ones, the lookahead rows zeros."""
+    w = np.zeros(shape, np.float32)
+    w[0] = 1.0
+    return w
+
+
+def row_conv_horizon_raw(cfg):
+    """(model frames, raw frames) the logits of a row-convolution model read past their own frame: tau, and that times the
+    subsampling factor plus the splice's right context."""
+    tau = row_conv_config(cfg)
+    return tau, tau * max(int(cfg.get("subsample") or 0), 1) + int(cfg.get("right_context") or 0)
+
+
+def row_conv_info_line(cfg):
+    """The INFO line of nnet-train / -validate / -forward / -align when the key is on, else None."""
+    tau = row_conv_config(cfg)
+    if not tau:
+        return None
+    _, raw = row_conv_horizon_raw(cfg)
+    return ("row convolution: row_conv_frames = %d: logits read %d model frames (%d raw frames) past their own"
+            % (tau, tau, raw))
+
+
 def chunk_horizon(num_layers, Nc, Nr, c=0, T=None):
     """H_L(c): the logits of chunk c of an L-layer latency-controlled BiLSTM (no splicing) read no input frame at or beyond
     it.  H_1 = (c + 1) Nc + Nr; a layer above reads its input up to H_l - 1, whose backward outputs come from the chunk that
@@ -324,6 +384,10 @@ class Model:
         # frames, as the same reverse recurrence on a re-laid-out batch of ceil(T / Nc) * B rows (lc_chunk_gather /
         # lc_chunk_fold).  Parameters and checkpoints are the plain model's.  fp32 only; refused otherwise.
         self.chunk, self.lookahead = chunk_config(self.cfg)
+        # Extension key row_conv_frames = tau (model frames; absent or 0: off, the plain model to the bit): the uni-LSTM's
+        # lookahead - one depthwise filter over the next tau frames of the top layer's output (after its batch norm), in front
+        # of the head (lc_row_conv_fwd / lc_row_conv_bwd).  Always fp32; one more parameter, row_conv/kernel.
+        self.row_conv = row_conv_config(self.cfg)
         self.device = torch.device(device)
         self.ps = ParamStore(self.cfg, self.device)
         self.ps.init_random(seed)
@@ -398,7 +462,10 @@ class Model:
 
     def lookahead_horizon(self):
         """Latency-controlled mode: the worst-case number of model frames past a chunk's end that its logits read,
-        H_L(0) - Nc (``chunk_horizon``); None when the mode is off (the whole utterance)."""
+        H_L(0) - Nc (``chunk_horizon``); None when the mode is off (the whole utterance).  A row-convolution model
+        (unidirectional): tau, the model frames its logits read past their own."""
+        if self.row_conv:
+            return self.row_conv
         if not self.chunk:
             return None
         return chunk_horizon(self.ps.num_layers, self.chunk, self.lookahead) - self.chunk
@@ -665,6 +732,12 @@ class Model:
                     ops.dropout_scale(Y, self.keep, drop_seed, 2 * i)
             layers.append(dict(inp=inp, inp_packed=inp_packed, dirs=dirs, cells=cells, Y=Y, residual=residual))
             inp = batch_norm("drnn_bn%d" % i, Y) if ps.use_bn else Y                  # lstm.py:288-294
+        pre_conv = None
+        if self.row_conv:
+            # lookahead: the head reads sum_j w[j] * top[t + j] over the live frames (fp32 in every compute_dtype; a fresh
+            # tensor, so the head product casts its own shadow).  The batch-normalised top is non-zero in dead frames: the
+            # pass never reads them.
+            pre_conv, inp = inp, ops.row_conv_fwd(inp, ps.p("row_conv/kernel"), seq_len, T, B)
         head = {}
         if ps.E > 0:
             a = self._mm(inp, ps.p("Variable"), bias=ps.p("Variable_1"))
@@ -674,7 +747,7 @@ class Model:
         else:
             logits = self._mm(inp, ps.p("Variable"), bias=ps.p("Variable_1"))
         self.saved = dict(layers=layers, head=head, T=T, B=B, seq_len=seq_len, drop_seed=drop_seed, bn=bn_saved,
-                          top=inp, frames=(pk_rows, pk_inverse) if self.packed else None,
+                          top=inp, pre_conv=pre_conv, frames=(pk_rows, pk_inverse) if self.packed else None,
                           chunks=(Tc, Bc, len_c) if chunked else None)
         return logits.view(T, B, ps.V)
 
@@ -759,6 +832,10 @@ class Model:
             dY = self._mm(dl, ps.p("Variable"), tb=True, epilogue=ep)
             self._mm(top, dl, ta=True, out=ps.g("Variable"))
             ops.colsum(dl, out=ps.g("Variable_1"))
+        if sv["pre_conv"] is not None:
+            # the row convolution's backward: the filter's gradient, and dY becomes the gradient of the tensor it read
+            dY, _ = ops.row_conv_bwd(sv["pre_conv"], dY, ps.p("row_conv/kernel"), sv["seq_len"], T, B,
+                                     dw=ps.g("row_conv/kernel"))
         for i in reversed(range(ps.num_layers)):
             L = sv["layers"][i]
             cells, dirs, inp = L["cells"], L["dirs"], L["inp"]

@@ -945,6 +945,70 @@ def chunk_fold(xc, T, B, chunk, lookahead, sum_copies=False, seq_len=None, out=N
     return out
 
 
+# ------------------------------------------------------------------------------------------ row convolution
+ROW_CONV_MAX_TAU = 32       # the library's design cap (include/lstm_ctc_hip.h)
+
+
+def _row_conv_args(w, seq_len, T, B, *mats):
+    assert w.dim() == 2 and w.dtype == torch.float32 and w.is_contiguous(), (w.shape, w.stride())
+    tau, C = w.shape[0] - 1, w.shape[1]
+    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+    for m in mats:
+        assert m.dim() == 2 and m.dtype == torch.float32 and m.stride(1) == 1 and tuple(m.shape) == (T * B, C), \
+            (tuple(m.shape), m.stride(), (T * B, C))
+    return tau, C
+
+
+def row_conv_fwd(x2d, w, seq_len, T, B, out=None):
+    """Row convolution (lc_row_conv_fwd): x2d [T*B, C] time-major f32 (a 2-D view, last stride 1), w [tau+1, C] dense, seq_len
+    [B] int32 -> out [T*B, C], out[t, b] = sum_j w[j] * x[t + j, b] over the live frames t + j of utterance b, +0 in dead rows.
+    Every element of out is written; dead rows of x are never read."""
+    lib = _lib.load()
+    _require_cuda(x2d, w, seq_len, out)
+    tau, C = _row_conv_args(w, seq_len, T, B, x2d)
+    if out is None:
+        out = torch.empty((T * B, C), dtype=torch.float32, device=x2d.device)
+    _row_conv_args(w, seq_len, T, B, out)
+    ev = _prof_begin()
+    _lib.check(lib.lc_row_conv_fwd(_ptr(x2d), _rows_pitch(x2d, C), _ptr(w), T, B, C, tau, _ptr(seq_len), _ptr(out),
+                                   _rows_pitch(out, C), _stream()), "lc_row_conv_fwd")
+    _prof_end("row_conv", 8.0 * T * B * C, ev)         # HBM bytes: x read once (the re-reads are L2's), y written
+    return out
+
+
+def row_conv_bwd(x2d, dy2d, w, seq_len, T, B, want_dx=True, want_dw=True, dx=None, dw=None):
+    """Gradients of row_conv_fwd (lc_row_conv_bwd) -> (dx [T*B, C] or None, dw [tau+1, C] or None): dx[t, b] = sum_j w[j] *
+    dy[t - j, b] in live rows, +0 in dead ones; dw[j] = sum over the live pairs of dy[t, b] * x[t + j, b], overwritten.
+    ``dx`` / ``dw``: optional destinations (dw dense).  The dw workspace is owned here."""
+    lib = _lib.load()
+    _require_cuda(x2d, dy2d, w, seq_len, dx, dw)
+    if not (want_dx or want_dw):
+        raise ValueError("row_conv_bwd: want_dx and want_dw are both false")
+    tau, C = _row_conv_args(w, seq_len, T, B, dy2d, *([x2d] if want_dw else []))
+    if want_dx:
+        if dx is None:
+            dx = torch.empty((T * B, C), dtype=torch.float32, device=dy2d.device)
+        _row_conv_args(w, seq_len, T, B, dx)
+    else:
+        dx = None
+    ws, nbytes = None, 0
+    if want_dw:
+        if dw is None:
+            dw = torch.empty((tau + 1, C), dtype=torch.float32, device=dy2d.device)
+        assert dw.dtype == torch.float32 and tuple(dw.shape) == (tau + 1, C) and dw.is_contiguous()
+        nbytes = lib.lc_row_conv_workspace_bytes(T, B, C, tau)
+        ws = workspace("row_conv", nbytes, dy2d.device)
+    else:
+        dw = None
+    xa = x2d if want_dw else None
+    ev = _prof_begin()
+    _lib.check(lib.lc_row_conv_bwd(_ptr(xa), _rows_pitch(xa, C) if xa is not None else C, _ptr(dy2d), _rows_pitch(dy2d, C),
+                                   _ptr(w), T, B, C, tau, _ptr(seq_len), _ptr(dx), _rows_pitch(dx, C) if dx is not None else C,
+                                   _ptr(dw), _ptr(ws), nbytes, _stream()), "lc_row_conv_bwd")
+    _prof_end("row_conv", 4.0 * T * B * C * (2 * bool(want_dx) + 2 * bool(want_dw)), ev)
+    return dx, dw
+
+
 # ------------------------------------------------------------------------------------------ SpecAugment
 def _tbd_pitch(t, T, B, D):
     """Row pitch of a time-major [T, B, D] tensor whose T * B rows lie at one pitch (a column window of a wider buffer is
