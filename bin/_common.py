@@ -1,5 +1,6 @@
 """Shared plumbing of the bin/nnet-*.py command lines (flag parsing quirks, device / process-group setup)."""
 import argparse
+import collections
 import os
 import sys
 
@@ -164,53 +165,11 @@ def report_label_windows(graph):
                % (graph.align_window, graph.windows_constrained, graph.windows_unconstrained))
 
 
-def delay_keywords(args):
-    """--delay-penalty: the graph keyword, empty without the flag (nnet-init has none).  The FATAL line and exit 1 when the
-    value is negative or not finite, or meets another objective than ctc.  Host work only: runs BEFORE the device is set up."""
-    penalty = getattr(args, 'delay_penalty', None)
-    if penalty is None:
-        return {}
+def _finite_nonnegative(value):
     import math
-    if not (math.isfinite(penalty) and penalty >= 0):
-        _fatal('--delay-penalty must be a finite number >= 0, got %r' % penalty)
-    if args.objective != 'ctc':
-        _fatal('--delay-penalty tilts the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
-    return {'delay_penalty': penalty}
-
-
-def report_delay_penalty(graph):
-    """One INFO line at the end of a pass under --delay-penalty: the mean frame at which a label is entered, under the
-    criterion's own path posterior."""
-    from lstm_ctc_amd.nnet import tflog
-    n = graph.entry_labels_total
-    tflog.info('delay penalty %g: mean label entry frame %.3f over %d label(s)'
-               % (graph.delay_penalty, graph.entry_sum_total / max(n, 1), n))
-
-
-def entropy_keywords(args):
-    """--entropy-weight: the graph keyword, empty without the flag (nnet-init has none).  The FATAL line and exit 1 when the
-    value is negative or not finite, meets another objective than ctc, or comes with --delay-penalty.  Host work only: runs
-    BEFORE the device is set up."""
-    weight = getattr(args, 'entropy_weight', None)
-    if weight is None:
-        return {}
-    import math
-    if not (math.isfinite(weight) and weight >= 0):
-        _fatal('--entropy-weight must be a finite number >= 0, got %r' % weight)
-    if args.objective != 'ctc':
-        _fatal('--entropy-weight regularises the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
-    if getattr(args, 'delay_penalty', None) is not None:
-        _fatal('--entropy-weight does not combine with --delay-penalty (the entropy of the tilted path posterior is not built)')
-    return {'entropy_weight': weight}
-
-
-def report_entropy_weight(graph):
-    """One INFO line at the end of a pass under --entropy-weight: the entropy of the posterior over the feasible paths, in
-    nats per utterance-frame."""
-    from lstm_ctc_amd.nnet import tflog
-    n = graph.path_entropy_frames_total
-    tflog.info('entropy weight %g: mean path entropy %.6f nats per frame over %d frame(s)'
-               % (graph.entropy_weight, graph.path_entropy_total / max(n, 1), n))
+    if not (math.isfinite(value) and value >= 0):
+        raise ValueError
+    return value
 
 
 def parse_star_penalty(text):
@@ -225,32 +184,71 @@ def parse_star_penalty(text):
     return values * 2 if len(values) == 1 else values
 
 
-def star_keywords(args):
-    """--star-penalty: the graph keyword, empty without the flag (nnet-init has none).  The FATAL line and exit 1 when the
-    value is not B[,S] with penalties >= 0 or inf, meets another objective than ctc, or comes with --delay-penalty or
-    --entropy-weight.  Host work only: runs BEFORE the device is set up."""
-    text = getattr(args, 'star_penalty', None)
-    if text is None:
-        return {}
+# The exclusive forms of the CTC criterion, by flag and in the order they are checked (nnet.graph.CRITERION_OPTIONS has the same
+# rows for the graph): parse (the flag's value -> the graph keyword's, or ValueError), "<flag> must be <must_be>", "<flag> <verb>
+# the CTC criterion", the earlier flags it refuses and the excuse in parentheses, the INFO line at the end of a pass, and the two
+# graph attributes that line reads after the graph's value(s): their quotient, then the second.
+_Flag = collections.namedtuple('_Flag', 'parse must_be verb refuses excuse line totals')
+CRITERION_FLAGS = {
+    '--delay-penalty': _Flag(_finite_nonnegative, 'a finite number >= 0', 'tilts', (), None,
+                             'delay penalty %g: mean label entry frame %.3f over %d label(s)',
+                             ('entry_sum_total', 'entry_labels_total')),
+    '--entropy-weight': _Flag(_finite_nonnegative, 'a finite number >= 0', 'regularises', ('--delay-penalty',),
+                              'the entropy of the tilted path posterior is not built',
+                              'entropy weight %g: mean path entropy %.6f nats per frame over %d frame(s)',
+                              ('path_entropy_total', 'path_entropy_frames_total')),
+    '--star-penalty': _Flag(parse_star_penalty, 'B[,S] with penalties >= 0 or inf', 'relaxes', ('--delay-penalty', '--entropy-weight'),
+                            'the star under that term is not built',
+                            'star penalty bypass %g selfloop %g: %.6f of %d frame(s) explained by the star',
+                            ('star_frames_total', 'star_frame_count_total')),
+}
+_attribute = lambda flag: flag.lstrip('-').replace('-', '_')
+
+
+def _parsed(flag, value):
     try:
-        penalty = parse_star_penalty(text)
+        return CRITERION_FLAGS[flag].parse(value)
     except ValueError as e:
-        _fatal('--star-penalty must be B[,S] with penalties >= 0 or inf, got %r (%s)' % (text, e))
-    if args.objective != 'ctc':
-        _fatal('--star-penalty relaxes the CTC criterion: it needs --objective ctc, not "%s"' % args.objective)
-    for other in ('delay_penalty', 'entropy_weight'):
-        if getattr(args, other, None) is not None:
-            _fatal('--star-penalty does not combine with --%s (the star under that term is not built)' % other.replace('_', '-'))
-    return {'star_penalty': penalty}
+        _fatal('%s must be %s, got %r%s' % (flag, CRITERION_FLAGS[flag].must_be, value, ' (%s)' % e if str(e) else ''))
 
 
-def report_star_penalty(graph):
-    """One INFO line at the end of a pass under --star-penalty: the share of the frames the star explains under the
-    criterion's path posterior."""
+def criterion_keywords(args, flags=tuple(CRITERION_FLAGS)):
+    """--delay-penalty, --entropy-weight, --star-penalty: the graph keywords of those given, empty without (nnet-init has
+    none).  Per flag, in the table's order, the FATAL line and exit 1 when parse refuses the value, when it meets another
+    objective than ctc, and when it comes with a flag it refuses.  Host work only: runs BEFORE the device is set up."""
+    keywords = {}
+    for flag in flags:
+        row, value = CRITERION_FLAGS[flag], getattr(args, _attribute(flag), None)
+        if value is None:
+            continue
+        keywords[_attribute(flag)] = _parsed(flag, value)
+        if args.objective != 'ctc':
+            _fatal('%s %s the CTC criterion: it needs --objective ctc, not "%s"' % (flag, row.verb, args.objective))
+        for other in row.refuses:
+            if getattr(args, _attribute(other), None) is not None:
+                _fatal('%s does not combine with %s (%s)' % (flag, other, row.excuse))
+    return keywords
+
+
+def report_criterion(graph, flags=tuple(CRITERION_FLAGS)):
+    """One INFO line at the end of a pass under the flag of CRITERION_FLAGS that is set: what the criterion's own path
+    posterior says - the mean frame at which a label is entered, the path entropy in nats per utterance-frame, the share of
+    the frames the star explains."""
     from lstm_ctc_amd.nnet import tflog
-    n = graph.star_frame_count_total
-    tflog.info('star penalty bypass %g selfloop %g: %.6f of %d frame(s) explained by the star'
-               % (graph.star_penalty[0], graph.star_penalty[1], graph.star_frames_total / max(n, 1), n))
+    for flag in flags:
+        row, value = CRITERION_FLAGS[flag], getattr(graph, _attribute(flag), None)
+        if value is not None:
+            total, n = (getattr(graph, name) for name in row.totals)
+            tflog.info(row.line % ((value if isinstance(value, tuple) else (value,)) + (total / max(n, 1), n)))
+
+
+# the table's rows one at a time, under their earlier names
+delay_keywords = lambda args: criterion_keywords(args, ('--delay-penalty',))
+entropy_keywords = lambda args: criterion_keywords(args, ('--entropy-weight',))
+star_keywords = lambda args: criterion_keywords(args, ('--star-penalty',))
+report_delay_penalty = lambda graph: report_criterion(graph, ('--delay-penalty',))
+report_entropy_weight = lambda graph: report_criterion(graph, ('--entropy-weight',))
+report_star_penalty = lambda graph: report_criterion(graph, ('--star-penalty',))
 
 
 def star_report_keywords(args):
@@ -261,10 +259,7 @@ def star_report_keywords(args):
         return {}
     if text is None or report is None:
         _fatal('--star-penalty and --star-report go together: the report is what the penalty is for')
-    try:
-        return {'star_penalty': parse_star_penalty(text)}
-    except ValueError as e:
-        _fatal('--star-penalty must be B[,S] with penalties >= 0 or inf, got %r (%s)' % (text, e))
+    return {'star_penalty': _parsed('--star-penalty', text)}
 
 
 def star_report_line(key, frames, labels, ctc_loss, star_loss, star_frames):

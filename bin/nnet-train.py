@@ -5,16 +5,14 @@ Launch under ``python -m torch.distributed.run --nproc-per-node N`` for utteranc
 import sys
 
 from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
-                     report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, delay_keywords,
-                     report_delay_penalty, spec_augment_keywords, report_spec_augment, consistency_keywords, report_consistency,
-                     report_chunking, report_row_conv, entropy_keywords, report_entropy_weight, star_keywords, report_star_penalty)
+                     report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, criterion_keywords,
+                     report_criterion, spec_augment_keywords, report_spec_augment, consistency_keywords, report_consistency,
+                     report_chunking, report_row_conv)
 
 
 def main(args):
     try:
-        delayed = delay_keywords(args)                    # --delay-penalty; fatal before the device is touched
-        regularised = entropy_keywords(args)              # --entropy-weight; likewise
-        tolerant = star_keywords(args)                    # --star-penalty; likewise
+        criterion = criterion_keywords(args)              # --delay-penalty / --entropy-weight / --star-penalty; fatal before the device
         augmented = spec_augment_keywords(args)           # --spec-augment; likewise
         paired = consistency_keywords(args, augmented)    # --consistency-weight; likewise
         frame_targets = read_frame_targets(args)          # xent, or ctc with --align-window; fatal before the device is touched
@@ -48,8 +46,7 @@ def main(args):
         windowed = {'align_window': args.align_window} if args.align_window is not None else {}
         graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, learn_rate=args.learn_rate,
                              clip_norm=args.clip_norm, optimizer=args.optimizer, device=device, seed=args.seed,
-                             process_group=pg, **windowed, **teacher_graph, **delayed, **regularised, **tolerant, **augmented,
-                             **paired)
+                             process_group=pg, **windowed, **teacher_graph, **criterion, **augmented, **paired)
         graph.restore(args.nnet_in)                       # trainable variables only; Adam slots restart
         sess = nnet.Session(graph)
         nnet.train(sess=sess, graph=graph, evaluate=args.evaluate, report_interval=args.report_interval)
@@ -59,12 +56,7 @@ def main(args):
             report_teacher_scores(pipeline, graph)
         if args.align_window is not None:
             report_label_windows(graph)
-        if delayed:
-            report_delay_penalty(graph)
-        if regularised:
-            report_entropy_weight(graph)
-        if tolerant:
-            report_star_penalty(graph)
+        report_criterion(graph)
         if augmented:
             report_spec_augment(graph)
         if paired:
@@ -82,7 +74,8 @@ if __name__ == '__main__':
     args = build_cli(('tfrecords_scp', 'nnet_config', 'nnet_in', 'nnet_out'),
                      ('--objective', '--optimizer', '--evaluate', '--learn-rate', '--batch-size', '--batch-threads',
                       '--seed', '--num-parallel-calls', '--report-interval', '--shuffle', '--clip-norm',
-                      '--frame-targets', '--align-window', '--delay-penalty', '--entropy-weight', '--star-penalty', '--spec-augment', '--consistency-weight', '--teacher-scores', '--teacher-domain', '--teacher-weight',
+                      '--frame-targets', '--align-window', '--delay-penalty', '--entropy-weight', '--star-penalty',
+                      '--spec-augment', '--consistency-weight', '--teacher-scores', '--teacher-domain', '--teacher-weight',
                       '--teacher-temperature')).parse_args()
     sys.stderr.write('INFO:tensorflow:' + ' '.join(sys.argv) + '\n')
     main(args)

@@ -4,15 +4,13 @@
 import sys
 
 from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
-                     report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, delay_keywords,
-                     report_delay_penalty, report_chunking, report_row_conv, entropy_keywords, report_entropy_weight, star_keywords, report_star_penalty)
+                     report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, criterion_keywords,
+                     report_criterion, report_chunking, report_row_conv)
 
 
 def run(args, init_only):
     try:
-        delayed = delay_keywords(args)                    # --delay-penalty; fatal before the device is touched
-        regularised = entropy_keywords(args)              # --entropy-weight; likewise
-        tolerant = star_keywords(args)                    # --star-penalty; likewise
+        criterion = criterion_keywords(args)              # --delay-penalty / --entropy-weight / --star-penalty; fatal before the device
         frame_targets = read_frame_targets(args)          # xent, or ctc with --align-window; fatal before the device is touched
         teacher = read_teacher_scores(args)               # --teacher-scores / --objective kd; likewise
         device, pg, rank, world = setup_device()
@@ -44,7 +42,7 @@ def run(args, init_only):
         align_window = getattr(args, 'align_window', None)      # nnet-init has no such flag
         windowed = {'align_window': align_window} if align_window is not None else {}
         graph = create_graph(pipeline=pipeline, nnet_config=nnet_config, device=device, seed=None if init_only else 123,
-                             **windowed, **teacher_graph, **delayed, **regularised, **tolerant)
+                             **windowed, **teacher_graph, **criterion)
         if init_only and pg is not None:                   # every rank must score the same random model
             from lstm_ctc_amd.nnet import dp
             dp.broadcast_(graph.model.ps.flat, pg, src=0)
@@ -59,12 +57,7 @@ def run(args, init_only):
             report_teacher_scores(pipeline, graph)
         if align_window is not None:
             report_label_windows(graph)
-        if delayed:
-            report_delay_penalty(graph)
-        if regularised:
-            report_entropy_weight(graph)
-        if tolerant:
-            report_star_penalty(graph)
+        report_criterion(graph)
         if init_only and rank == 0:
             tflog.info('saving nnet to "%s"' % args.nnet_out)
             graph.save(args.nnet_out)
@@ -77,8 +70,9 @@ def run(args, init_only):
 def build_parser(init_only):
     return build_cli(('tfrecords_scp', 'nnet_config', 'nnet_out' if init_only else 'nnet_in'),
                      ('--objective', '--evaluate', '--batch-size', '--batch-threads', '--report-interval',
-                      '--frame-targets') + (() if init_only else ('--align-window', '--delay-penalty', '--entropy-weight', '--star-penalty', '--teacher-scores', '--teacher-domain', '--teacher-weight',
-                                                                '--teacher-temperature')))
+                      '--frame-targets') + (() if init_only else (
+                          '--align-window', '--delay-penalty', '--entropy-weight', '--star-penalty', '--teacher-scores',
+                          '--teacher-domain', '--teacher-weight', '--teacher-temperature')))
 
 
 if __name__ == '__main__':

@@ -12,6 +12,7 @@ so ``nnet.train`` / ``nnet.validate`` (funcs.py) read exactly like the reference
   gradient buffer is summed with ONE RCCL all-reduce before the clip, so N ranks x B utterances
   reproduce a single batch of N*B (the clip at graph.py:190 acts on the total gradient of a SUM loss).
 """
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -203,6 +204,46 @@ def _checked_number(name, value, lower, strict, must_be, integer=False):
     return int(value) if integer else float(value)
 
 
+def _needs_ctc(keyword, verb, objective):
+    if objective != "ctc":
+        raise ValueError("%s %s the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % (keyword, verb, objective))
+
+
+class _CriterionOption(namedtuple("_CriterionOption", "keyword check verb under excuse op as_args keys counts totals minus_extra",
+                                  defaults=(False,))):
+    """One row of CRITERION_OPTIONS: an alternative form of the CTC criterion, of which a graph takes at most one.
+    ``check(value)`` -> the value the graph keeps, or ValueError; ``verb`` fills "<keyword> <verb> the CTC criterion"; ``excuse``
+    stands in parentheses when the option meets an EARLIER row (whose ``under`` fills its %(under)s); ``op`` names the
+    ``ops`` function - looked up per call - that takes ``as_args(value)`` after max_label_len and returns (loss[B], extra[B],
+    grad); ``keys`` are the two output keys, the sum of extra and the sum of ``counts`` ("labels" or "frames") over the
+    utterances with a finite, non-skipped loss; ``totals`` the attributes that sum them over the steps; ``minus_extra``:
+    eval_loss is (loss - value * extra).sum() instead of loss.sum()."""
+
+    def call(self, value, logits, flat_d, offs_d, seq_d, maxlen, **kw):
+        return getattr(ops, self.op)(logits, flat_d, offs_d, seq_d, maxlen, *self.as_args(value), **kw)
+
+
+def _nonnegative(keyword):
+    return lambda value: _checked_number(keyword, value, 0, False, "a finite float >= 0 or None")
+
+
+# Adding an exclusive CTC criterion option: one row here (in the order the constructor checks them), its ``ops`` wrapper, its
+# keyword in CTCGraph.__init__ - and its row in bin/_common.py CRITERION_FLAGS.
+CRITERION_OPTIONS = {option.keyword: option for option in (
+    _CriterionOption("delay_penalty", _nonnegative("delay_penalty"), "tilts", "delay tilt", None,
+                     "ctc_loss_delay", lambda v: (v,), ("entry_sum", "entry_labels"), "labels",
+                     ("entry_sum_total", "entry_labels_total")),
+    _CriterionOption("entropy_weight", _nonnegative("entropy_weight"), "regularises", "entropy term",
+                     "the entropy of the tilted path posterior is not built",
+                     "ctc_loss_entropy", lambda v: (v,), ("path_entropy", "path_entropy_frames"), "frames",
+                     ("path_entropy_total", "path_entropy_frames_total"), minus_extra=True),
+    _CriterionOption("star_penalty", _checked_star_penalty, "relaxes", "star",
+                     "the star under the %(under)s is not built",
+                     "ctc_loss_star", tuple, ("star_frames", "star_frame_count"), "frames",
+                     ("star_frames_total", "star_frame_count_total")),
+)}
+
+
 class CTCGraph:
     """Validation (and, with ``learn_rate``, training) graph over a batch pipeline.
 
@@ -302,37 +343,26 @@ class CTCGraph:
         self.needs_teacher = objective == "kd" or teacher_weight is not None
         self.kd_frames_total = self.kd_agree_total = 0
         if align_window is not None:
-            if objective != "ctc":
-                raise ValueError("align_window constrains the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
+            _needs_ctc("align_window", "constrains", objective)
             align_window = _checked_number("align_window", align_window, 0, False, "an int >= 0 (frames) or None",
                                            integer=True)
         self.align_window = align_window
         self.windows_constrained = self.windows_unconstrained = 0
-        if delay_penalty is not None:
-            if objective != "ctc":
-                raise ValueError("delay_penalty tilts the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
-            delay_penalty = _checked_number("delay_penalty", delay_penalty, 0, False, "a finite float >= 0 or None")
-        self.delay_penalty = delay_penalty
-        self.entry_sum_total, self.entry_labels_total = 0.0, 0
-        if entropy_weight is not None:
-            if objective != "ctc":
-                raise ValueError("entropy_weight regularises the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
-            entropy_weight = _checked_number("entropy_weight", entropy_weight, 0, False, "a finite float >= 0 or None")
-            if delay_penalty is not None:
-                raise ValueError("entropy_weight does not combine with delay_penalty (the entropy of the tilted path "
-                                 "posterior is not built)")
-        self.entropy_weight = entropy_weight
-        self.path_entropy_total, self.path_entropy_frames_total = 0.0, 0
-        if star_penalty is not None:
-            if objective != "ctc":
-                raise ValueError("star_penalty relaxes the CTC criterion: it needs objective=\"ctc\", not \"%s\"" % objective)
-            star_penalty = _checked_star_penalty(star_penalty)
-            if delay_penalty is not None:
-                raise ValueError("star_penalty does not combine with delay_penalty (the star under the delay tilt is not built)")
-            if entropy_weight is not None:
-                raise ValueError("star_penalty does not combine with entropy_weight (the star under the entropy term is not built)")
-        self.star_penalty = star_penalty
-        self.star_frames_total, self.star_frame_count_total = 0.0, 0
+        given = dict(delay_penalty=delay_penalty, entropy_weight=entropy_weight, star_penalty=star_penalty)
+        self._criterion_option = None                    # at most one row of CRITERION_OPTIONS
+        for option in CRITERION_OPTIONS.values():
+            value = given[option.keyword]
+            if value is not None:
+                _needs_ctc(option.keyword, option.verb, objective)
+                value = option.check(value)
+                earlier = self._criterion_option
+                if earlier is not None:
+                    raise ValueError("%s does not combine with %s (%s)"
+                                     % (option.keyword, earlier.keyword, option.excuse % {"under": earlier.under}))
+                self._criterion_option = option
+            setattr(self, option.keyword, value)
+            setattr(self, option.totals[0], 0.0)
+            setattr(self, option.totals[1], 0)
         self.spec_layout = None
         if spec_augment is not None:
             from . import augment
@@ -343,9 +373,7 @@ class CTCGraph:
         self.spec_augment = spec_augment
         self.specaug_steps = 0
         if consistency_weight is not None:
-            if objective != "ctc":
-                raise ValueError("consistency_weight pairs two views under the CTC criterion: it needs objective=\"ctc\", "
-                                 "not \"%s\"" % objective)
+            _needs_ctc("consistency_weight", "pairs two views under", objective)
             consistency_weight = _checked_number("consistency_weight", consistency_weight, 0, True,
                                                  "a finite float > 0 or None")
             if teacher_weight is not None:
@@ -632,51 +660,32 @@ class CTCGraph:
     # host, reduced at the step's one copy; ``outputs(host, out, fetch_eval)`` writing size, eval_loss, eval and its own keys
     # into ``out`` from the fetched {name: float} - and adding to its ``*_total`` counters, so only for a step that completed.
     def _ctc_criterion(self, logits, b, train):
-        entry_b = entropy_b = star_b = None
-        if self.delay_penalty is not None:
-            lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
-            loss_b, entry_b, grad = ops.ctc_loss_delay(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.delay_penalty,
-                                                       win_lo=lo_d, win_hi=hi_d, want_grad=train)
-        elif self.entropy_weight is not None:
-            lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
-            loss_b, entropy_b, grad = ops.ctc_loss_entropy(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.entropy_weight,
-                                                           win_lo=lo_d, win_hi=hi_d, want_grad=train)
-        elif self.star_penalty is not None:
-            lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
-            loss_b, star_b, grad = ops.ctc_loss_star(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, self.star_penalty[0],
-                                                     self.star_penalty[1], win_lo=lo_d, win_hi=hi_d, want_grad=train)
+        option = self._criterion_option
+        lo_d, hi_d = b.windows if self.align_window is not None else (None, None)
+        extra_b = None
+        if option is not None:
+            value = getattr(self, option.keyword)
+            loss_b, extra_b, grad = option.call(value, logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, win_lo=lo_d, win_hi=hi_d,
+                                                want_grad=train)
         elif self.align_window is not None:
-            loss_b, grad = ops.ctc_loss_windowed(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, b.windows[0], b.windows[1],
-                                                 want_grad=train)
+            loss_b, grad = ops.ctc_loss_windowed(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, lo_d, hi_d, want_grad=train)
         else:
             loss_b, grad = ops.ctc_loss(logits, b.flat_d, b.offs_d, b.seq_d, b.maxlen, want_grad=train)
 
         def scalars():
-            if entropy_b is not None:                                            # the criterion: sum of loss - eta * H
-                return ([("eval_loss", (loss_b - self.entropy_weight * entropy_b).sum())]
-                        + list(zip(("path_entropy", "path_entropy_frames"),
-                                   self._entropy_scalars(loss_b, entropy_b, b.offs_d, b.seq_d))))
-            pairs = [("eval_loss", loss_b.sum())]                                # graph.py:116 reduce_sum, in float32
-            if entry_b is not None:
-                pairs += zip(("entry_sum", "entry_labels"), self._entry_scalars(loss_b, entry_b, b.offs_d, b.seq_d))
-            if star_b is not None:                                               # the same selection and sums as the entropy's
-                pairs += zip(("star_frames", "star_frame_count"), self._entropy_scalars(loss_b, star_b, b.offs_d, b.seq_d))
-            return pairs
+            if option is None:
+                return [("eval_loss", loss_b.sum())]                             # graph.py:116 reduce_sum, in float32
+            total = (loss_b - value * extra_b if option.minus_extra else loss_b).sum()
+            labels_b = (b.offs_d[1:] - b.offs_d[:-1]).to(torch.int64)
+            sums = self._selected_sums(loss_b, extra_b, labels_b, b.seq_d, labels_b if option.counts == "labels" else b.seq_d)
+            return [("eval_loss", total)] + list(zip(option.keys, sums))
 
         def outputs(host, out, fetch_eval):                  # (``eval`` needs the greedy decode: the tail's)
             out["size"], out["eval_loss"] = b.size, host["eval_loss"]
-            if entry_b is not None:
-                out["entry_sum"], out["entry_labels"] = host["entry_sum"], int(host["entry_labels"])
-                self.entry_sum_total += out["entry_sum"]
-                self.entry_labels_total += out["entry_labels"]
-            if entropy_b is not None:
-                out["path_entropy"], out["path_entropy_frames"] = host["path_entropy"], int(host["path_entropy_frames"])
-                self.path_entropy_total += out["path_entropy"]
-                self.path_entropy_frames_total += out["path_entropy_frames"]
-            if star_b is not None:
-                out["star_frames"], out["star_frame_count"] = host["star_frames"], int(host["star_frame_count"])
-                self.star_frames_total += out["star_frames"]
-                self.star_frame_count_total += out["star_frame_count"]
+            if option is not None:
+                for key, total, kind in zip(option.keys, option.totals, (float, int)):
+                    out[key] = kind(host[key])
+                    setattr(self, total, getattr(self, total) + out[key])
         return grad, scalars, outputs
 
     def _xent_criterion(self, logits, b, train):
@@ -710,22 +719,14 @@ class CTCGraph:
         return [t.to(torch.float64).sum() for t in tensors]
 
     @staticmethod
-    def _entry_scalars(loss_b, entry_b, offs_d, seq_d):
-        """delay_penalty: [sum of entry_sum, number of labels] over the utterances with a finite, non-skipped loss."""
-        n = (offs_d[1:] - offs_d[:-1]).to(torch.int64)
-        ok = torch.isfinite(loss_b) & (seq_d > 0) & (n <= seq_d)
+    def _selected_sums(loss_b, extra_b, labels_b, seq_d, count_b):
+        """A criterion option's two scalars: [float64 sum of extra_b, int64 sum of count_b] over the utterances with a finite,
+        non-skipped loss (frames, and no more labels - labels_b, int64 - than frames).  count_b: labels_b for delay_penalty,
+        seq_d for entropy_weight and star_penalty."""
+        ok = torch.isfinite(loss_b) & (seq_d > 0) & (labels_b <= seq_d)
         zero = torch.zeros((), dtype=torch.float64, device=loss_b.device)
-        return [torch.where(ok, entry_b.to(torch.float64), zero).sum(), torch.where(ok, n, torch.zeros_like(n)).sum()]
-
-    @staticmethod
-    def _entropy_scalars(loss_b, entropy_b, offs_d, seq_d):
-        """entropy_weight (and star_penalty, with star_frames as ``entropy_b``): [sum of entropy, sum of seq_len] over the
-        utterances with a finite, non-skipped loss."""
-        n = (offs_d[1:] - offs_d[:-1]).to(torch.int64)
-        ok = torch.isfinite(loss_b) & (seq_d > 0) & (n <= seq_d)
-        zero = torch.zeros((), dtype=torch.float64, device=loss_b.device)
-        frames = seq_d.to(torch.int64)
-        return [torch.where(ok, entropy_b.to(torch.float64), zero).sum(), torch.where(ok, frames, torch.zeros_like(frames)).sum()]
+        count_b = count_b.to(torch.int64)
+        return [torch.where(ok, extra_b.to(torch.float64), zero).sum(), torch.where(ok, count_b, torch.zeros_like(count_b)).sum()]
 
     def _kd_outputs(self, out, host):
         """Writes kd_loss / kd_frames / kd_agree into ``out`` and returns what the term adds to ``loss``."""
@@ -821,8 +822,9 @@ class CTCGraph:
         ``star_penalty=(pb, ps)`` (new) adds ``ctc_loss``, ``star_loss`` and ``star_frames``, each [B] float32: ``ops.ctc_loss``
         and ``ops.ctc_loss_star`` on the same logits, no gradient - what a per-utterance transcript report is written from;
         ``ali``, ``label_index`` and ``score`` are what they are without it."""
+        star = CRITERION_OPTIONS["star_penalty"]
         if star_penalty is not None:
-            star_penalty = _checked_star_penalty(star_penalty)
+            star_penalty = star.check(star_penalty)
         x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = self._upload(batch)
         self._validate_labels(flat)
         model, dev = self.model, self.model.device
@@ -835,8 +837,7 @@ class CTCGraph:
                 res = ops.ctc_align(logits, flat_d, offs_d, seq_d, maxlen)
                 if star_penalty is not None:
                     plain, _ = ops.ctc_loss(logits, flat_d, offs_d, seq_d, maxlen, want_grad=False)
-                    star_loss, star_frames, _ = ops.ctc_loss_star(logits, flat_d, offs_d, seq_d, maxlen, star_penalty[0],
-                                                                  star_penalty[1], want_grad=False)
+                    star_loss, star_frames, _ = star.call(star_penalty, logits, flat_d, offs_d, seq_d, maxlen, want_grad=False)
                     res = tuple(res) + (plain, star_loss, star_frames)
                 return res, int(ops.lstm_status(dev).item())
 
@@ -943,23 +944,29 @@ def load_params(ps, path):
 
 
 # ----------------------------------------------------------------------------------------------------- reference-named factories
+def _criterion_only(options):
+    """A CTC factory's ``**criterion``: the keywords of CRITERION_OPTIONS pass to CTCGraph, anything else is the TypeError of a
+    keyword the factory does not take (a validation graph takes no spec_augment, say)."""
+    for name in options:
+        if name not in CRITERION_OPTIONS:
+            raise TypeError("got an unexpected keyword argument %r" % name)
+    return options
+
+
 def create_graph_for_validation_ctc(pipeline, nnet_config, device="cuda", seed=None, align_window=None,
-                                    teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, entropy_weight=None,
-                                    star_penalty=None):
+                                    teacher_weight=None, teacher_temperature=1.0, **criterion):
     return CTCGraph(pipeline, nnet_config, device=device, seed=seed, align_window=align_window,
-                    teacher_weight=teacher_weight, teacher_temperature=teacher_temperature, delay_penalty=delay_penalty,
-                    entropy_weight=entropy_weight, star_penalty=star_penalty)
+                    teacher_weight=teacher_weight, teacher_temperature=teacher_temperature, **_criterion_only(criterion))
 
 
 def create_graph_for_training_ctc(pipeline, nnet_config, learn_rate, clip_norm=5.0, optimizer="sgd",
                                   l2_decay_weight=1e-5, device="cuda", seed=None, process_group=None, align_window=None,
-                                  teacher_weight=None, teacher_temperature=1.0, delay_penalty=None, spec_augment=None,
-                                  consistency_weight=None, entropy_weight=None, star_penalty=None):
+                                  teacher_weight=None, teacher_temperature=1.0, spec_augment=None, consistency_weight=None,
+                                  **criterion):
     return CTCGraph(pipeline, nnet_config, learn_rate=learn_rate, clip_norm=clip_norm, optimizer=optimizer,
                     l2_decay_weight=l2_decay_weight, device=device, seed=seed, process_group=process_group,
                     align_window=align_window, teacher_weight=teacher_weight, teacher_temperature=teacher_temperature,
-                    delay_penalty=delay_penalty, spec_augment=spec_augment, consistency_weight=consistency_weight,
-                    entropy_weight=entropy_weight, star_penalty=star_penalty)
+                    spec_augment=spec_augment, consistency_weight=consistency_weight, **_criterion_only(criterion))
 
 
 def create_graph_for_validation_xent(pipeline, nnet_config, device="cuda", seed=None, teacher_weight=None,

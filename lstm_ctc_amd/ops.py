@@ -266,25 +266,60 @@ def dropout_scale(x, keep, seed, stream_id, out=None, accumulate=False, shadow=N
 
 
 # ------------------------------------------------------------------------------------------ CTC
-def ctc_loss(logits, labels, offsets, seq_len, max_label_len, want_grad=True):
-    """logits [T,B,V] f32; labels flat int32; offsets [B+1] int32; seq_len [B] int32 (all on device).
-    Returns (loss[B], grad[T,B,V] or None)."""
+# The lattice entries of include/lstm_ctc_hip.h, by the wrapper that calls them: (C entry, its workspace query, workspace
+# name, windows - None: the entry takes none, "required", "optional" - and whether a [B] output follows ``loss``).
+_LATTICE = {
+    "ctc_loss": ("lc_ctc_loss", "lc_ctc_workspace_bytes", "ctc", None, False),
+    "ctc_loss_windowed": ("lc_ctc_loss_windowed", "lc_ctc_window_workspace_bytes", "ctc_window", "required", False),
+    "ctc_loss_delay": ("lc_ctc_loss_delay", "lc_ctc_delay_workspace_bytes", "ctc_delay", "optional", True),
+    "ctc_loss_entropy": ("lc_ctc_loss_entropy", "lc_ctc_entropy_workspace_bytes", "ctc_entropy", "optional", True),
+    "ctc_loss_star": ("lc_ctc_loss_star", "lc_ctc_star_workspace_bytes", "ctc_star", "optional", True),
+}
+
+
+def _ctc_lattice_call(who, logits, labels, offsets, seq_len, max_label_len, win_lo=None, win_hi=None, scalars=(),
+                      want_grad=True, want_extra=True):
+    """The one body under the five CTC wrappers: ``who`` names the wrapper (its row of _LATTICE, and the errors' prefix),
+    ``scalars`` are the floats the entry takes between win_hi and loss.  Returns (loss[B], extra[B] or None, grad[T,B,V] or
+    None); extra is None as well for an entry that has none."""
+    entry, query, pool, windows, has_extra = _LATTICE[who]
     lib = _lib.load()
-    _require_cuda(logits, labels, offsets, seq_len)
+    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
     logits = _f32c(logits)
     T, B, V = logits.shape
     assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
+    if windows == "optional" and (win_lo is None) != (win_hi is None):
+        raise ValueError("%s: win_lo and win_hi go together (both or none)" % who)
+    if windows == "required" or win_lo is not None:
+        assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
+        if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
+            raise ValueError("%s: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
+                             % (who, win_lo.numel(), win_hi.numel(), labels.numel()))
+        win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
     loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    extra = torch.empty(B, dtype=torch.float32, device=logits.device) if has_extra and want_extra else None
     grad = torch.empty_like(logits) if want_grad else None
-    nbytes = lib.lc_ctc_workspace_bytes(T, B, V, int(max_label_len))
-    ws = workspace("ctc", nbytes, logits.device)
-    if labels.numel() == 0:
+    nbytes = getattr(lib, query)(T, B, V, int(max_label_len))
+    ws = workspace(pool, nbytes, logits.device)
+    if labels.numel() == 0:                                                  # an empty vector has no address to pass
         labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
+        if win_lo is not None:
+            win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
+            win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    args = [_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len)]
+    if windows is not None:
+        args += [_ptr(win_lo), _ptr(win_hi)]
+    args += [float(s) for s in scalars] + [_ptr(loss)] + ([_ptr(extra)] if has_extra else []) + [_ptr(grad), _ptr(ws), nbytes]
     ev = _prof_begin()
-    _lib.check(lib.lc_ctc_loss(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len),
-                               int(max_label_len), _ptr(loss), _ptr(grad), _ptr(ws), nbytes, _stream()),
-               "lc_ctc_loss")
+    _lib.check(getattr(lib, entry)(*args, _stream()), entry)
     _prof_end("ctc", (T, B, V), ev)
+    return loss, extra, grad
+
+
+def ctc_loss(logits, labels, offsets, seq_len, max_label_len, want_grad=True):
+    """logits [T,B,V] f32; labels flat int32; offsets [B+1] int32; seq_len [B] int32 (all on device).
+    Returns (loss[B], grad[T,B,V] or None)."""
+    loss, _, grad = _ctc_lattice_call("ctc_loss", logits, labels, offsets, seq_len, max_label_len, want_grad=want_grad)
     return loss, grad
 
 
@@ -293,29 +328,8 @@ def ctc_loss_windowed(logits, labels, offsets, seq_len, max_label_len, win_lo, w
     on the device, parallel to the flat labels; label j may sit on frame t only when win_lo[j] <= t <= win_hi[j] (values
     outside the utterance clip; see :func:`label_windows`).  Returns (loss[B], grad[T,B,V] or None) over the surviving paths;
     +inf and a softmax gradient where no path survives."""
-    lib = _lib.load()
-    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
-    logits = _f32c(logits)
-    T, B, V = logits.shape
-    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
-    assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
-    if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
-        raise ValueError("ctc_loss_windowed: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
-                         % (win_lo.numel(), win_hi.numel(), labels.numel()))
-    win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
-    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
-    grad = torch.empty_like(logits) if want_grad else None
-    nbytes = lib.lc_ctc_window_workspace_bytes(T, B, V, int(max_label_len))
-    ws = workspace("ctc_window", nbytes, logits.device)
-    if labels.numel() == 0:
-        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
-        win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
-        win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
-    ev = _prof_begin()
-    _lib.check(lib.lc_ctc_loss_windowed(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len),
-                                        int(max_label_len), _ptr(win_lo), _ptr(win_hi), _ptr(loss), _ptr(grad), _ptr(ws),
-                                        nbytes, _stream()), "lc_ctc_loss_windowed")
-    _prof_end("ctc", (T, B, V), ev)
+    loss, _, grad = _ctc_lattice_call("ctc_loss_windowed", logits, labels, offsets, seq_len, max_label_len, win_lo, win_hi,
+                                      want_grad=want_grad)
     return loss, grad
 
 
@@ -325,37 +339,10 @@ def ctc_loss_delay(logits, labels, offsets, seq_len, max_label_len, delay_penalt
     finite float: a path is weighted by exp(-lambda * sum of the frames at which its labels are entered)) and, optionally,
     the windows of :func:`ctc_loss_windowed` (both or none).  Returns (loss[B], entry_sum[B] or None, grad[T,B,V] or None):
     entry_sum is the expected sum of the label entry frames under the penalised path posterior, = d loss / d lambda."""
-    lib = _lib.load()
-    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
-    logits = _f32c(logits)
-    T, B, V = logits.shape
-    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
     if isinstance(delay_penalty, bool) or not np.isfinite(delay_penalty):
         raise ValueError("ctc_loss_delay: delay_penalty must be a finite float, got %r" % (delay_penalty,))
-    if (win_lo is None) != (win_hi is None):
-        raise ValueError("ctc_loss_delay: win_lo and win_hi go together (both or none)")
-    if win_lo is not None:
-        assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
-        if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
-            raise ValueError("ctc_loss_delay: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
-                             % (win_lo.numel(), win_hi.numel(), labels.numel()))
-        win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
-    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
-    entry = torch.empty(B, dtype=torch.float32, device=logits.device) if want_entry else None
-    grad = torch.empty_like(logits) if want_grad else None
-    nbytes = lib.lc_ctc_delay_workspace_bytes(T, B, V, int(max_label_len))
-    ws = workspace("ctc_delay", nbytes, logits.device)
-    if labels.numel() == 0:
-        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
-        if win_lo is not None:
-            win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
-            win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
-    ev = _prof_begin()
-    _lib.check(lib.lc_ctc_loss_delay(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len),
-                                     _ptr(win_lo), _ptr(win_hi), float(delay_penalty), _ptr(loss), _ptr(entry), _ptr(grad),
-                                     _ptr(ws), nbytes, _stream()), "lc_ctc_loss_delay")
-    _prof_end("ctc", (T, B, V), ev)
-    return loss, entry, grad
+    return _ctc_lattice_call("ctc_loss_delay", logits, labels, offsets, seq_len, max_label_len, win_lo, win_hi,
+                             (delay_penalty,), want_grad, want_entry)
 
 
 def ctc_loss_entropy(logits, labels, offsets, seq_len, max_label_len, entropy_weight, win_lo=None, win_hi=None, want_grad=True):
@@ -363,37 +350,10 @@ def ctc_loss_entropy(logits, labels, offsets, seq_len, max_label_len, entropy_we
     entropy_weight (eta, any finite float) and, optionally, the windows of :func:`ctc_loss_windowed` (both or none).
     Returns (loss[B], entropy[B], grad[T,B,V] or None): loss is plain (windowed) CTC's, entropy the entropy in nats of the
     posterior over the feasible paths, grad the exact gradient of ``loss - entropy_weight * entropy``."""
-    lib = _lib.load()
-    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
-    logits = _f32c(logits)
-    T, B, V = logits.shape
-    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
     if isinstance(entropy_weight, bool) or not np.isfinite(entropy_weight):
         raise ValueError("ctc_loss_entropy: entropy_weight must be a finite float, got %r" % (entropy_weight,))
-    if (win_lo is None) != (win_hi is None):
-        raise ValueError("ctc_loss_entropy: win_lo and win_hi go together (both or none)")
-    if win_lo is not None:
-        assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
-        if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
-            raise ValueError("ctc_loss_entropy: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
-                             % (win_lo.numel(), win_hi.numel(), labels.numel()))
-        win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
-    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
-    entropy = torch.empty(B, dtype=torch.float32, device=logits.device)
-    grad = torch.empty_like(logits) if want_grad else None
-    nbytes = lib.lc_ctc_entropy_workspace_bytes(T, B, V, int(max_label_len))
-    ws = workspace("ctc_entropy", nbytes, logits.device)
-    if labels.numel() == 0:
-        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
-        if win_lo is not None:
-            win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
-            win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
-    ev = _prof_begin()
-    _lib.check(lib.lc_ctc_loss_entropy(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len),
-                                       _ptr(win_lo), _ptr(win_hi), float(entropy_weight), _ptr(loss), _ptr(entropy),
-                                       _ptr(grad), _ptr(ws), nbytes, _stream()), "lc_ctc_loss_entropy")
-    _prof_end("ctc", (T, B, V), ev)
-    return loss, entropy, grad
+    return _ctc_lattice_call("ctc_loss_entropy", logits, labels, offsets, seq_len, max_label_len, win_lo, win_hi,
+                             (entropy_weight,), want_grad)
 
 
 def ctc_loss_star(logits, labels, offsets, seq_len, max_label_len, bypass_penalty, selfloop_penalty, win_lo=None, win_hi=None,
@@ -403,38 +363,11 @@ def ctc_loss_star(logits, labels, offsets, seq_len, max_label_len, bypass_penalt
     :func:`ctc_loss_windowed` (both or none).  Returns (loss[B], star_frames[B], grad[T,B,V] or None): loss is -log of the path
     sum over the lattice whose cells may explain a frame by the penalised star (it may be negative), star_frames the expected
     number of frames the star explains under the path posterior, grad the exact gradient of loss."""
-    lib = _lib.load()
-    _require_cuda(logits, labels, offsets, seq_len, win_lo, win_hi)
-    logits = _f32c(logits)
-    T, B, V = logits.shape
-    assert labels.dtype == torch.int32 and offsets.dtype == torch.int32 and seq_len.dtype == torch.int32
     for name, p in (("bypass_penalty", bypass_penalty), ("selfloop_penalty", selfloop_penalty)):
         if isinstance(p, bool) or not p >= 0:                                   # NaN fails the comparison
             raise ValueError("ctc_loss_star: %s must be a float >= 0 or +inf, got %r" % (name, p))
-    if (win_lo is None) != (win_hi is None):
-        raise ValueError("ctc_loss_star: win_lo and win_hi go together (both or none)")
-    if win_lo is not None:
-        assert win_lo.dtype == torch.int32 and win_hi.dtype == torch.int32
-        if win_lo.numel() != labels.numel() or win_hi.numel() != labels.numel():
-            raise ValueError("ctc_loss_star: win_lo / win_hi must be parallel to labels (%d, %d, %d elements)"
-                             % (win_lo.numel(), win_hi.numel(), labels.numel()))
-        win_lo, win_hi = win_lo.contiguous(), win_hi.contiguous()
-    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
-    star = torch.empty(B, dtype=torch.float32, device=logits.device)
-    grad = torch.empty_like(logits) if want_grad else None
-    nbytes = lib.lc_ctc_star_workspace_bytes(T, B, V, int(max_label_len))
-    ws = workspace("ctc_star", nbytes, logits.device)
-    if labels.numel() == 0:
-        labels = torch.zeros(1, dtype=torch.int32, device=logits.device)
-        if win_lo is not None:
-            win_lo = torch.zeros(1, dtype=torch.int32, device=logits.device)
-            win_hi = torch.zeros(1, dtype=torch.int32, device=logits.device)
-    ev = _prof_begin()
-    _lib.check(lib.lc_ctc_loss_star(_ptr(logits), T, B, V, _ptr(labels), _ptr(offsets), _ptr(seq_len), int(max_label_len),
-                                    _ptr(win_lo), _ptr(win_hi), float(bypass_penalty), float(selfloop_penalty), _ptr(loss),
-                                    _ptr(star), _ptr(grad), _ptr(ws), nbytes, _stream()), "lc_ctc_loss_star")
-    _prof_end("ctc", (T, B, V), ev)
-    return loss, star, grad
+    return _ctc_lattice_call("ctc_loss_star", logits, labels, offsets, seq_len, max_label_len, win_lo, win_hi,
+                             (bypass_penalty, selfloop_penalty), want_grad)
 
 
 WINDOW_OPEN = np.iinfo(np.int32).max
@@ -506,6 +439,22 @@ def ctc_align(logits, labels, offsets, seq_len, max_label_len, want_label_index=
     return ali, lidx, score
 
 
+def _frame_outputs(B, dev):
+    """The [B] outputs of a frame loss: (loss f32, frames i32, a second count i32), uninitialised."""
+    return (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+            torch.empty(B, dtype=torch.int32, device=dev))
+
+
+def _grad_to_fill(who, shape, logits, grad, want_grad):
+    """(grad, accumulate) of kd_loss / consistency_loss: a given ``grad`` - contiguous float32 of the logits' shape, ``shape``
+    in the error's words - is accumulated into (1); else (0) a new one is overwritten, or None without ``want_grad``."""
+    if grad is not None:
+        if grad.dtype != torch.float32 or grad.shape != logits.shape or not grad.is_contiguous():
+            raise ValueError("%s: grad must be a contiguous float32 %s tensor to accumulate into" % (who, shape))
+        return grad, 1
+    return (torch.empty_like(logits) if want_grad else None), 0
+
+
 def xent_loss(logits, targets, seq_len, want_grad=True):
     """Frame-level softmax cross-entropy - no reference counterpart.  logits [T,B,V] f32; targets [B,T] int32, one symbol
     per frame as :func:`ctc_align` writes them (the blank V-1 is a legal target, -1 = ignore); seq_len [B] int32.
@@ -522,9 +471,7 @@ def xent_loss(logits, targets, seq_len, want_grad=True):
                          % (B, T, tuple(targets.shape), tuple(seq_len.shape)))
     targets = targets.contiguous()
     dev = logits.device
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    frames = torch.empty(B, dtype=torch.int32, device=dev)
-    correct = torch.empty(B, dtype=torch.int32, device=dev)
+    loss, frames, correct = _frame_outputs(B, dev)
     grad = torch.empty_like(logits) if want_grad else None
     nbytes = lib.lc_xent_workspace_bytes(T, B, V)
     ws = workspace("xent", nbytes, dev)
@@ -552,22 +499,15 @@ def kd_loss(logits, teacher, seq_len, teacher_len, temperature=1.0, grad_scale=1
     if tuple(teacher.shape) != (T, B, V) or seq_len.numel() != B or teacher_len.numel() != B:
         raise ValueError("kd_loss: teacher must be [T, B, V] = [%d, %d, %d], seq_len and teacher_len [B] (got %s, %s, %s)"
                          % (T, B, V, tuple(teacher.shape), tuple(seq_len.shape), tuple(teacher_len.shape)))
-    accumulate = grad is not None
-    if accumulate:
-        if grad.dtype != torch.float32 or tuple(grad.shape) != (T, B, V) or not grad.is_contiguous():
-            raise ValueError("kd_loss: grad must be a contiguous float32 [T, B, V] tensor to accumulate into")
-    elif want_grad:
-        grad = torch.empty_like(logits)
+    grad, accumulate = _grad_to_fill("kd_loss", "[T, B, V]", logits, grad, want_grad)
     dev = logits.device
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    frames = torch.empty(B, dtype=torch.int32, device=dev)
-    agree = torch.empty(B, dtype=torch.int32, device=dev)
+    loss, frames, agree = _frame_outputs(B, dev)
     nbytes = lib.lc_kd_workspace_bytes(T, B, V)
     ws = workspace("kd", nbytes, dev)
     ev = _prof_begin()
     _lib.check(lib.lc_kd_loss(_ptr(logits), _ptr(teacher), T, B, V, _ptr(seq_len.contiguous()), _ptr(teacher_len.contiguous()),
                               float(temperature), float(grad_scale), _ptr(loss), _ptr(frames), _ptr(agree), _ptr(grad),
-                              1 if accumulate else 0, _ptr(ws), nbytes, _stream()), "lc_kd_loss")
+                              accumulate, _ptr(ws), nbytes, _stream()), "lc_kd_loss")
     _prof_end("kd", (T, B, V), ev)
     return loss, frames, agree, grad
 
@@ -590,21 +530,14 @@ def consistency_loss(logits, seq_len, grad_scale=1.0, grad=None, want_grad=True)
     if B2 != 2 * B or B == 0:
         raise ValueError("consistency_loss: logits must be [T, 2B, V] for seq_len [B] (got %s, %s)"
                          % (tuple(logits.shape), tuple(seq_len.shape)))
-    accumulate = grad is not None
-    if accumulate:
-        if grad.dtype != torch.float32 or tuple(grad.shape) != (T, B2, V) or not grad.is_contiguous():
-            raise ValueError("consistency_loss: grad must be a contiguous float32 [T, 2B, V] tensor to accumulate into")
-    elif want_grad:
-        grad = torch.empty_like(logits)
+    grad, accumulate = _grad_to_fill("consistency_loss", "[T, 2B, V]", logits, grad, want_grad)
     dev = logits.device
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    frames = torch.empty(B, dtype=torch.int32, device=dev)
-    agree = torch.empty(B, dtype=torch.int32, device=dev)
+    loss, frames, agree = _frame_outputs(B, dev)
     nbytes = lib.lc_consistency_workspace_bytes(T, B, V)
     ws = workspace("consistency", nbytes, dev)
     ev = _prof_begin()
     _lib.check(lib.lc_consistency_loss(_ptr(logits), T, B, V, _ptr(seq_len.contiguous()), float(grad_scale), _ptr(loss),
-                                       _ptr(frames), _ptr(agree), _ptr(grad), 1 if accumulate else 0, _ptr(ws), nbytes,
+                                       _ptr(frames), _ptr(agree), _ptr(grad), accumulate, _ptr(ws), nbytes,
                                        _stream()), "lc_consistency_loss")
     _prof_end("consistency", (T, B, V), ev)
     return loss, frames, agree, grad
