@@ -2629,37 +2629,62 @@ inline unsigned persist_spin_limit()
     return v < 0 ? 0u : (unsigned)v;
 }
 thread_local int g_last_sched = 0;
-// Geometry of the persistent schedule, or false when the shape does not qualify (then the launch train runs).
-inline bool persist_geom(int T, int B, int N, int ndir, bool bwd, PGeom &g, size_t &lds_bytes)
-{
-    // read per call: the tests compare the two schedules, and a failed launch is re-run with the override set
-    if (lc_option(LC_OPT_LSTM_PERSISTENT, 1) == 0 || N > P_MAXN || N % 16 != 0 || T < 4 || !persist_device_ok()) return false;
-    g.T = T; g.B = B; g.N = N; g.ndir = ndir;
-    g.gpd = 8 / ndir;
-    g.rpg = lc_cdiv(B, g.gpd);
-    if (g.rpg > 16) return false;
-    g.upw = (lc_cdiv(N, 32) + 3) & ~3;
-    g.UP = g.upw;
-    g.nwg = lc_cdiv(N, g.upw);
-    // LDS holds only the partial tiles; the request is nevertheless more than half a CU's LDS so that two slices can
-    // never share a CU (and its matrix pipe) while other CUs idle - 76 KB stay free for co-resident GEMM workgroups
-    (void)bwd;
-    lds_bytes = 84 * 1024;
-    return true;
-}
-inline bool persist_geom_bf16(int T, int B, int N, int ndir, PGeom &g, size_t &lds_bytes)
-{
-    if (lc_option(LC_OPT_LSTM_PERSISTENT, 1) == 0 || N > 1024 || N % 32 != 0 || T < 4 || !persist_device_ok()) return false;
-    g.T = T; g.B = B; g.N = N; g.ndir = ndir;
-    g.gpd = 8 / ndir;
-    g.rpg = lc_cdiv(B, g.gpd);
-    if (g.rpg > 16) return false;
-    g.upw = (lc_cdiv(N, 32) + 3) & ~3;
-    g.UP = g.upw;
-    g.nwg = lc_cdiv(N, g.upw);
-    lds_bytes = 84 * 1024;
-    return true;
-}
+
+// ---- the kernels of every schedule, one table per argument block ---------------------------------------------------
+// (the tables list exactly the instantiations a call can reach; a new kernel variant is one row here and one branch of
+// lstm_plan below)
+#define LC_BOTH(K, ...) K<__VA_ARGS__, true>, K<__VA_ARGS__, false>
+#define LC_BOTH8(K) LC_BOTH(K, 1), LC_BOTH(K, 2), LC_BOTH(K, 3), LC_BOTH(K, 4), LC_BOTH(K, 5), LC_BOTH(K, 6), LC_BOTH(K, 7), LC_BOTH(K, 8)
+#define LC_EVEN16(K) K<2>, K<4>, K<6>, K<8>, K<10>, K<12>, K<14>, K<16>
+inline int both(int row, bool first) { return 2 * row + (first ? 0 : 1); }      // index into rows of LC_BOTH
+constexpr void (*FWD_STEP_KERNELS[])(FwdArgs) = {LC_BOTH(lstm_fwd_step_kernel, 1), LC_BOTH(lstm_fwd_step_kernel, 2),      // [MT - 1][bf16 first]
+                                                 LC_BOTH(lstm_fwd_step_kernel, 3), LC_BOTH(lstm_fwd_step_kernel, 4)};
+constexpr void (*BWD_STEP_KERNELS[])(BwdArgs) = {LC_BOTH(lstm_bwd_step_kernel, 1), LC_BOTH(lstm_bwd_step_kernel, 2)};
+// single-XCD schedules: fp32 [ceil(N / 64) - 1][ragged (N % 64) first], split-operand [N / 64 - 1], bf16 [fwd: ceil(N / 128) - 1,
+// bwd: ceil(N / 256) - 1][ragged first], and last the bf16 shadow-only form of the full width
+enum { PK_F32 = 0, PK_X3 = 16, PK_BF16 = 24, PK_FWD_SHONLY = 40, PK_BWD_SHONLY = 32 };
+constexpr void (*PFWD_KERNELS[])(PFwdArgs) = {
+    LC_BOTH8(lstm_fwd_persist_kernel), LC_EVEN16(lstm_fwd_persist_x3_kernel),
+    LC_BOTH(lstm_fwd_persist_bf16_kernel, 1, 1), LC_BOTH(lstm_fwd_persist_bf16_kernel, 2, 1), LC_BOTH(lstm_fwd_persist_bf16_kernel, 3, 1),
+    LC_BOTH(lstm_fwd_persist_bf16_kernel, 4, 1), LC_BOTH(lstm_fwd_persist_bf16_kernel, 5, 2), LC_BOTH(lstm_fwd_persist_bf16_kernel, 6, 2),
+    LC_BOTH(lstm_fwd_persist_bf16_kernel, 7, 2), LC_BOTH(lstm_fwd_persist_bf16_kernel, 8, 2), lstm_fwd_persist_bf16_kernel<8, 2, false, true>};
+constexpr void (*PBWD_KERNELS[])(PBwdArgs) = {
+    LC_BOTH8(lstm_bwd_persist_kernel), LC_EVEN16(lstm_bwd_persist_x3_kernel),
+    LC_BOTH(lstm_bwd_persist_bf16_kernel, 1, 1), LC_BOTH(lstm_bwd_persist_bf16_kernel, 2, 1), LC_BOTH(lstm_bwd_persist_bf16_kernel, 3, 2),
+    LC_BOTH(lstm_bwd_persist_bf16_kernel, 4, 2), lstm_bwd_persist_bf16_kernel<4, 2, false, true>};
+// XCD-pair schedule: fp32 [N / 128 - 5], then split-operand N = 768, 1024
+constexpr void (*XFWD_KERNELS[])(XFwdArgs) = {lstm_fwd_pair_kernel<5>, lstm_fwd_pair_kernel<6>, lstm_fwd_pair_kernel<7>,
+                                              lstm_fwd_pair_kernel<8>, lstm_fwd_pair_x3_kernel<6>, lstm_fwd_pair_x3_kernel<8>};
+constexpr void (*XBWD_KERNELS[])(XBwdArgs) = {lstm_bwd_pair_kernel<5>, lstm_bwd_pair_kernel<6>, lstm_bwd_pair_kernel<7>,
+                                              lstm_bwd_pair_kernel<8>, lstm_bwd_pair_x3_kernel<6>, lstm_bwd_pair_x3_kernel<8>};
+#undef LC_BOTH
+#undef LC_BOTH8
+#undef LC_EVEN16
+
+// ---- the schedule plan: where a call's schedule is decided, once ---------------------------------------------------
+enum Sched {          // bits 0-7 of lc_debug_last_lstm_schedule() (lstm_ctc_hip.h)
+    SCHED_PERSIST = 1, SCHED_PERSIST_BF16 = 2, SCHED_TWO_STREAM = 3, SCHED_TRAIN = 4, SCHED_PAIR = 5, SCHED_PAIR_X3 = 6,
+    SCHED_PERSIST_X3 = 7
+};
+inline bool sched_pair(int kind) { return kind == SCHED_PAIR || kind == SCHED_PAIR_X3; }
+enum Shadow { SHADOW_NONE, SHADOW_KERNEL, SHADOW_PASS };      // who writes hs_bf16 / dz_bf16: nobody (no such entry), the kernel, a pass behind it
+struct Plan {
+    int kind = SCHED_TRAIN;
+    bool bwd, bf16;
+    bool split = false;            // the split-operand (x3) kernel of the schedule is taken
+    bool two_stream = false;       // launch train: one chain per direction if a second stream is to be had (then SCHED_TWO_STREAM, mt = 2)
+    int mt = 0;                    // launch train: 16-row tiles per workgroup
+    PGeom g;                       // single-XCD schedules (XCD-pair: nwg alone, the workgroups per XCD that hold a slice)
+    int kernel = 0;                // row of the schedule's table above
+    int kernel_shadow_only = -1;   // ... when every direction asks for shadow_only, if the schedule has such a form
+    size_t lds = 0;                // dynamic LDS bytes
+    size_t clear_bytes = 0;        // persistent schedules: the workspace bytes cleared before a launch, and what fills the exchange buffers
+    int clear_fill = 0;
+    int rows_per_launch = 0;       // XCD-pair schedule
+    bool shadow32 = false;         // the x3 shadow of dz ([T * B, 12 N] bf16) fits the kernels' 32-bit byte offsets
+    Shadow shadow = SHADOW_NONE;
+};
+
 // The XCD-pair schedule (fp32, 1024-unit layers: config c4).  One launch drives two "direction slots" of four XCDs, 64
 // batch rows each.  Both directions of a layer: slot d = direction d, and batches of more than 64 rows run as
 // ceil(B / 64) launches back to back over 64-row blocks (the tensors keep their [T, B, *] layout: a slot has a row base,
@@ -2667,46 +2692,137 @@ inline bool persist_geom_bf16(int T, int B, int N, int ndir, PGeom &g, size_t &l
 // direction, 128 rows per launch.
 // widths the pair kernels are instantiated for: N = 128 NKB, NKB = 5 .. 8 (below 640 the single-XCD schedule holds R)
 inline bool pair_width(int N) { return N == 640 || N == 768 || N == 896 || N == 1024; }
-inline bool pair_x3_width(int N) { return N == 768 || N == 1024; }     // ... and for the split-operand kernels (whole 32-blocks)
-inline bool persist_x3_width(int N) { return N >= 64 && N <= 512 && N % 64 == 0; }     // single-XCD kernels, split operands
+// The persistent schedule a width has kernels for, whatever T, B, the options and the device say (0: none): the plan starts
+// from it and the workspace is sized for it.  Split operands (x3): the XCD-pair kernels at N = 768 / 1024 and the single-XCD
+// ones at N = 64 .. 512 in steps of 64 (whole 32-blocks); every other width runs the fp32 kernels (same arithmetic in
+// another summation order).  (The entries have refused N % 16 != 0, and N % 32 != 0 for bf16, before they plan.)
+inline int width_sched(bool bf, bool x3, int N)
+{
+    if (!bf && pair_width(N)) return x3 && (N == 768 || N == 1024) ? SCHED_PAIR_X3 : SCHED_PAIR;
+    if (N % 16 != 0 || N > (bf ? 1024 : P_MAXN)) return 0;
+    return bf ? SCHED_PERSIST_BF16 : (x3 && N % 64 == 0) ? SCHED_PERSIST_X3 : SCHED_PERSIST;
+}
 inline bool pair_geom(int T, int B, int N, int ndir)
 {
     // (the kernels address their [T, B, 4N] tensors with unsigned 32-bit scalar frame offsets)
     return lc_option(LC_OPT_LSTM_PERSISTENT, 1) != 0 && pair_width(N) && (ndir == 1 || ndir == 2) && B >= 1 && T >= 4 &&
            (unsigned long long)T * B * 4 * N * sizeof(float) <= 0xffffffffull && persist_device_ok();
 }
-inline int pair_rows_per_launch(int ndir) { return ndir == 2 ? 64 : 128; }
-inline size_t pair_fwd_ws_bytes() { return P_CTL_BYTES + (X_HX_FLOATS + X_PX_FLOATS) * sizeof(float); }
-inline size_t pair_bwd_ws_bytes() { return P_CTL_BYTES + (XB_DZX_FLOATS + XB_PX_FLOATS) * sizeof(float); }
-inline size_t pair_bwd_x3_ws_bytes() { return P_CTL_BYTES + (X3B_DZX_FLOATS + XB_PX_FLOATS) * sizeof(float); }     // producer-split pieces: 1.5 x
-inline size_t persist_ws_bytes(int N, bool bwd)
+// Geometry of the single-XCD schedule, or false when the shape does not qualify (then the launch train runs).
+inline bool persist_geom(int T, int B, int N, int ndir, PGeom &g)
 {
-    if (N > 1024 || N % 16 != 0) return 0;
-    return P_CTL_BYTES + (size_t)8 * 2 * (bwd ? 4 * N : 2 * N) * 16 * sizeof(float);
-}
-inline size_t persist_bwd_x3_ws_bytes(int N) { return P_CTL_BYTES + (size_t)8 * 2 * x3p_bwd_buf_bytes(N); }     // producer-split pieces: 1.5 x
-inline size_t upg_part_bytes(int N) { return al256((size_t)2 * UPG_SPLITS * 7 * N * sizeof(float)); }   // x 2: both directions of the XCD-pair BPTT at once
-
-// rows of the transposed [K][Bpad] state buffers: covers every row a workgroup row-tile touches
-inline int bpad(int B) { return B <= 16 ? 16 : (B <= 64 ? ((B + 31) & ~31) : ((B + 63) & ~63)); }
-
-// Clears what a persistent launch needs cleared: the per-launch part of the control block (NOT the sticky status word)
-// and the exchange buffers behind it.
-inline bool persist_clear(void *workspace, size_t ws_bytes, hipStream_t s, int fill = 0)
-{
-    // (fill = 0xff: the bf16 BPTT's exchange buffers start out as "not arrived" sentinels)
-    return hipMemsetAsync(workspace, 0, LC_LSTM_STATUS_OFFSET, s) == hipSuccess &&
-           hipMemsetAsync((char *)workspace + P_CTL_BYTES, fill, ws_bytes - P_CTL_BYTES, s) == hipSuccess;
-}
-
-template <class K, class A>
-inline bool persist_launch(K kernel, size_t lds, hipStream_t s, const A &args)
-{
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return false;
-    hipLaunchKernelGGL(kernel, dim3(P_GRID), dim3(P_THREADS), lds, s, args);
+    // read per call: the tests compare the two schedules, and a failed launch is re-run with the override set
+    if (lc_option(LC_OPT_LSTM_PERSISTENT, 1) == 0 || T < 4 || !persist_device_ok()) return false;
+    g.T = T; g.B = B; g.N = N; g.ndir = ndir;
+    g.gpd = 8 / ndir;
+    g.rpg = lc_cdiv(B, g.gpd);
+    if (g.rpg > 16) return false;
+    g.upw = (lc_cdiv(N, 32) + 3) & ~3;
+    g.UP = g.upw;
+    g.nwg = lc_cdiv(N, g.upw);
     return true;
 }
+// rows of the transposed [K][Bpad] state buffers: covers every row a workgroup row-tile touches
+inline int bpad(int B) { return B <= 16 ? 16 : (B <= 64 ? ((B + 31) & ~31) : ((B + 63) & ~63)); }
+// launch train: bytes of a direction's state buffers (forward: hT ping-pong; backward: dzT ping-pong, then dc) and of its packed weights
+inline size_t train_pingpong_bytes(bool bwd, int B, int N) { return al256((size_t)2 * (bwd ? 4 * N : N) * bpad(B) * sizeof(float)); }
+inline size_t train_state_bytes(bool bwd, int B, int N)
+{
+    return train_pingpong_bytes(bwd, B, N) + (bwd ? al256((size_t)B * N * sizeof(float)) : 0);
+}
+inline size_t train_weight_bytes(int N) { return al256((size_t)N * 4 * N * sizeof(float)); }
+// Workspace layout: [control block P_CTL_BYTES][schedule-specific buffers]: the bytes a schedule uses, control block included
+inline size_t sched_ws_bytes(int kind, bool bwd, int B, int N, int ndir)
+{
+    const size_t single = P_CTL_BYTES + (size_t)8 * 2 * (bwd ? 4 * N : 2 * N) * 16 * sizeof(float);
+    const size_t pair = P_CTL_BYTES + (bwd ? XB_DZX_FLOATS + XB_PX_FLOATS : X_HX_FLOATS + X_PX_FLOATS) * sizeof(float);
+    switch (kind) {
+    case SCHED_PERSIST: case SCHED_PERSIST_BF16: return single;
+    case SCHED_PERSIST_X3: return bwd ? P_CTL_BYTES + (size_t)8 * 2 * x3p_bwd_buf_bytes(N) : single;     // producer-split pieces: 1.5 x
+    case SCHED_PAIR: return pair;
+    case SCHED_PAIR_X3: return bwd ? P_CTL_BYTES + (X3B_DZX_FLOATS + XB_PX_FLOATS) * sizeof(float) : pair;      // ... likewise
+    default: return P_CTL_BYTES + (size_t)ndir * (train_state_bytes(bwd, B, N) + train_weight_bytes(N));
+    }
+}
+
+// Everything the walks below need to know about a call's schedule, from its shape, the two options and the device alone.
+inline Plan lstm_plan(bool bwd, bool bf, bool x3, int T, int B, int N, int ndir)
+{
+    Plan p;
+    p.bwd = bwd; p.bf16 = bf;
+    const int built = width_sched(bf, x3, N);
+    if (sched_pair(built) && pair_geom(T, B, N, ndir)) {
+        p.kind = built;
+        p.split = built == SCHED_PAIR_X3;
+        p.kernel = p.split ? 4 + (N == 1024) : N / 128 - 5;
+        p.lds = !p.split ? (size_t)84 * 1024 : bwd ? x3_bwd_lds_bytes(N / 128) : x3_fwd_lds_bytes(N / 128);
+        p.g.nwg = N / 32;
+        p.rows_per_launch = ndir == 2 ? 64 : 128;
+    } else if (built && !sched_pair(built) && persist_geom(T, B, N, ndir, p.g)) {
+        p.kind = built;
+        p.split = built == SCHED_PERSIST_X3;
+        p.kernel = p.split ? PK_X3 + N / 64 - 1
+                 : !bf     ? PK_F32 + both(lc_cdiv(N, 64) - 1, N % 64 != 0)
+                 : bwd     ? PK_BF16 + both(lc_cdiv(N, 256) - 1, N % 256 != 0)
+                           : PK_BF16 + both(lc_cdiv(N, 128) - 1, N % 128 != 0);
+        if (bf && N == 1024) p.kernel_shadow_only = bwd ? PK_BWD_SHONLY : PK_FWD_SHONLY;
+        // LDS holds only the partial tiles; the request is nevertheless more than half a CU's LDS so that two slices can
+        // never share a CU (and its matrix pipe) while other CUs idle - 76 KB stay free for co-resident GEMM workgroups
+        p.lds = 84 * 1024;
+        p.clear_fill = bf ? 0xff : 0;          // the bf16 kernels' exchange buffers start out as "not arrived" sentinels
+    } else if (bwd) {
+        // 32-row tiles: (N/16) x (B/32) x ndir workgroups of [32 x 16] outputs - 256 of them at N=1024, B=64
+        // ... and 16-row tiles when that grid would leave most of the 256 CUs idle (N = 320 / 512 at B = 32: 40 / 64
+        // workgroups -> 80 / 128; measured 7.4 -> 5.9 and 9.2 -> 7.0 us per step)
+        p.mt = bpad(B) >= 32 && (long long)(N / 16) * lc_cdiv(B, 32) * ndir >= 200 ? 2 : 1;
+    } else {
+        // Row tile: 64 rows per workgroup when that already fills the chip (N = 1024: 256 workgroups; more, smaller
+        // tiles re-stream R and measured 18.5 vs 15.1 us), halved while the grid would leave CUs idle (N = 320 / 512 at
+        // B = 32: 5.4 -> 4.7 and 6.3 -> 5.3 us per step).
+        p.mt = bpad(B) >= 64 ? 4 : bpad(B) / 16;
+        while (p.mt > 1 && (long long)(N / 8) * lc_cdiv(B, 16 * p.mt) * ndir < 200) p.mt = (p.mt + 1) / 2;
+        p.two_stream = !bf && ndir == 2 && bpad(B) == 64 && N >= 1024;      // (see lstm_fwd_walk)
+    }
+    if (p.kind != SCHED_TRAIN) p.clear_bytes = sched_ws_bytes(p.kind, bwd, B, N, ndir);
+    p.shadow32 = (unsigned long long)T * B * 12 * N * 2 <= 0x7fffffffull;
+    // hs_bf16 / dz_bf16: the bf16 persistent kernels write it next to hs / dz, and the split-operand BPTT kernels' producers,
+    // which split dz anyway, write the x3 shadow of dz (lc_lstm_bwd_x3) while its byte offsets fit their 32-bit buffer
+    // addressing; every other schedule gets a cast / split pass behind the recurrence
+    if (bf) p.shadow = p.kind == SCHED_PERSIST_BF16 ? SHADOW_KERNEL : SHADOW_PASS;
+    else if (x3 && bwd) p.shadow = p.split && p.shadow32 ? SHADOW_KERNEL : SHADOW_PASS;
+    return p;
+}
+// The schedule word (lstm_ctc_hip.h).  x3_shadow_written: bit 18, the kernel's producers wrote the x3 shadow of dz.
+inline int sched_word(const Plan &p, bool x3_shadow_written)
+{
+    return p.kind | (p.mt << 8) | ((int)p.bf16 << 16) | ((int)p.bwd << 17) | ((int)x3_shadow_written << 18);
+}
+
+// ---- what the two passes' direction records have in common ---------------------------------------------------------
+inline bool dir_complete(const lc_lstm_fwd_dir_t &d) { return d.zx && d.R && d.cs && d.hs; }
+inline bool dir_complete(const lc_lstm_bwd_dir_t &d) { return d.gates && d.RT && d.cs && d.dh; }
+inline float *dir_out(const lc_lstm_fwd_dir_t &d) { return d.hs; }            // the output a failed persistent launch poisons
+inline float *dir_out(const lc_lstm_bwd_dir_t &d) { return d.gates; }
+inline uint16_t *dir_shadow(const lc_lstm_fwd_dir_t &d) { return d.hs_bf16; }
+inline uint16_t *dir_shadow(const lc_lstm_bwd_dir_t &d) { return d.dz_bf16; }
+// A direction as the kernels take it; the launch train fills in its state buffers and packed weights itself.
+inline DirFwd dir_args(const lc_lstm_fwd_dir_t &d, bool shadow)
+{
+    DirFwd a;
+    a.zx = d.zx; a.R = d.R; a.w_f = d.w_f; a.w_i = d.w_i; a.w_o = d.w_o;
+    a.cs = d.cs; a.hs = d.hs; a.hT = nullptr; a.reverse = d.reverse;
+    a.hs16 = shadow ? d.hs_bf16 : nullptr;
+    return a;
+}
+inline DirBwd dir_args(const lc_lstm_bwd_dir_t &d, bool shadow)
+{
+    DirBwd a;
+    a.gates = d.gates; a.RT = d.RT; a.w_f = d.w_f; a.w_i = d.w_i; a.w_o = d.w_o;
+    a.cs = d.cs; a.dh = d.dh; a.dc = nullptr; a.dzT = nullptr; a.reverse = d.reverse;
+    a.dz16 = shadow ? d.dz_bf16 : nullptr;
+    return a;
+}
+inline bool wants_unit_grads(const lc_lstm_bwd_dir_t &d) { return (d.dpeep && d.w_f) || d.dbias; }
 
 }  // namespace
 
@@ -2714,30 +2830,22 @@ inline bool persist_launch(K kernel, size_t lds, hipStream_t s, const A &args)
 extern "C" void lc_debug_set_lstm_stamps(unsigned long long *buf) { g_lstm_dbg = buf; }
 extern "C" int lc_debug_last_lstm_schedule(void) { return g_last_sched; }
 
-// Workspace layout: [control block P_CTL_BYTES][schedule-specific buffers]; the backward one ends with the partial
-// sums of the bias / peephole gradient reduce.
-extern "C" size_t lc_lstm_fwd_workspace_bytes(int B, int N, int ndir)
+// The workspace holds whatever schedule a call of this (B, N, ndir) can land on - the launch train, or the persistent one
+// each of the three entries has kernels for at this width -; the backward one ends with the partial sums of the bias /
+// peephole gradient reduce (x 2: both directions of the XCD-pair BPTT at once).
+static size_t lstm_main_bytes(bool bwd, int B, int N, int ndir)
 {
-    size_t need = P_CTL_BYTES + (size_t)ndir * (al256((size_t)2 * N * bpad(B) * sizeof(float)) +
-                                                al256((size_t)N * 4 * N * sizeof(float)));
-    if (al256(persist_ws_bytes(N, false)) > need) need = al256(persist_ws_bytes(N, false));
-    if (pair_width(N) && al256(pair_fwd_ws_bytes()) > need) need = al256(pair_fwd_ws_bytes());
+    size_t need = sched_ws_bytes(SCHED_TRAIN, bwd, B, N, ndir);
+    for (int entry = 0; entry < 3; ++entry) {            // fp32, split-operand, bf16
+        const int kind = width_sched(entry == 2, entry == 1, N);
+        if (kind && al256(sched_ws_bytes(kind, bwd, B, N, ndir)) > need) need = al256(sched_ws_bytes(kind, bwd, B, N, ndir));
+    }
     return need;
 }
-static size_t lstm_bwd_main_bytes(int B, int N, int ndir)
-{
-    size_t need = P_CTL_BYTES + (size_t)ndir * (al256((size_t)2 * 4 * N * bpad(B) * sizeof(float)) +
-                                                al256((size_t)B * N * sizeof(float)) +
-                                                al256((size_t)N * 4 * N * sizeof(float)));
-    if (al256(persist_ws_bytes(N, true)) > need) need = al256(persist_ws_bytes(N, true));
-    if (pair_width(N) && al256(pair_bwd_ws_bytes()) > need) need = al256(pair_bwd_ws_bytes());
-    if (pair_x3_width(N) && al256(pair_bwd_x3_ws_bytes()) > need) need = al256(pair_bwd_x3_ws_bytes());
-    if (persist_x3_width(N) && al256(persist_bwd_x3_ws_bytes(N)) > need) need = al256(persist_bwd_x3_ws_bytes(N));
-    return need;
-}
+extern "C" size_t lc_lstm_fwd_workspace_bytes(int B, int N, int ndir) { return lstm_main_bytes(false, B, N, ndir); }
 extern "C" size_t lc_lstm_bwd_workspace_bytes(int B, int N, int ndir)
 {
-    return lstm_bwd_main_bytes(B, N, ndir) + upg_part_bytes(N);
+    return lstm_main_bytes(true, B, N, ndir) + al256((size_t)2 * UPG_SPLITS * 7 * N * sizeof(float));
 }
 
 // Second in-order queue (per device) for the two-stream forward schedule, plus the fork / join events.  Two internal
@@ -2786,481 +2894,302 @@ static void pack_operand(bool bf, const float *W, int K, int C, void *dst, hipSt
     else hipLaunchKernelGGL(pack_k16_kernel, dim3(1024), dim3(256), 0, s, W, K, C, (float *)dst);
 }
 
-template <bool BF>
-static void launch_fwd_step(int mt, dim3 grid, hipStream_t s, const FwdArgs &a)
-{
-    dim3 block(NTHREADS);
-    switch (mt) {
-    case 1: hipLaunchKernelGGL((lstm_fwd_step_kernel<1, BF>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((lstm_fwd_step_kernel<2, BF>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((lstm_fwd_step_kernel<3, BF>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((lstm_fwd_step_kernel<4, BF>), grid, block, 0, s, a); break;
-    }
-}
-
-// x3: the step product as fp32-on-bf16x3 (lstm_pair_x3.inc) where a split-operand kernel exists for the shape - the XCD-pair
-// schedule at N = 768 / 1024, the single-XCD schedule at N = 64 .. 512 in steps of 64 -; every other shape, and the launch-train fall-back, runs the fp32 kernels (same arithmetic in
-// another summation order).
-static int lstm_fwd_impl(bool bf, bool x3, const char *who, const lc_lstm_fwd_dir_t *dirs, int ndir, const int *seq_len, int T,
-                         int B, int N, float forget_bias, void *workspace, size_t workspace_bytes, lc_stream_t stream)
+// ---- what the two walks share ----------------------------------------------------------------------------------------
+template <class D>
+static int lstm_check_args(const char *who, bool bwd, bool bf, const D *dirs, int ndir, const int *seq_len, int T, int B, int N,
+                           void *workspace, size_t workspace_bytes)
 {
     LC_CHECK_ARG(dirs && seq_len && workspace, "%s: null pointer", who);
     LC_CHECK_ARG(ndir == 1 || ndir == 2, "%s: ndir must be 1 or 2", who);
     LC_CHECK_ARG(T > 0 && B > 0 && N > 0 && N % (bf ? 32 : 16) == 0, "%s: need T,B > 0 and num_neurons %% %d == 0 (N=%d)",
                  who, bf ? 32 : 16, N);
-    if (workspace_bytes < lc_lstm_fwd_workspace_bytes(B, N, ndir)) {
+    if (workspace_bytes < (bwd ? lc_lstm_bwd_workspace_bytes(B, N, ndir) : lc_lstm_fwd_workspace_bytes(B, N, ndir))) {
         lc_set_error("%s: workspace too small", who);
         return LC_EWORKSPACE;
     }
+    for (int i = 0; i < ndir; ++i) LC_CHECK_ARG(dir_complete(dirs[i]), "%s: null pointer in dirs[%d]", who, i);
+    return LC_OK;
+}
+
+// One persistent launch: clear, launch, verify.  `count`: elements of a direction's output (dir_out).
+template <class K, class A, class D>
+static int persist_run(const Plan &p, const char *who, const char *what, K kernel, const A &args, void *workspace, const D *dirs,
+                       int ndir, size_t count, hipStream_t s)
+{
+    // cleared: the per-launch part of the control block (NOT the sticky status word) and the exchange buffers behind it
+    if (hipMemsetAsync(workspace, 0, LC_LSTM_STATUS_OFFSET, s) != hipSuccess ||
+        hipMemsetAsync((char *)workspace + P_CTL_BYTES, p.clear_fill, p.clear_bytes - P_CTL_BYTES, s) != hipSuccess) {
+        lc_set_error("%s: memset failed", who);
+        return LC_ELAUNCH;
+    }
+    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) {
+        lc_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the %s kernel", who,
+                     sched_pair(p.kind) ? "XCD-pair" : "persistent");
+        (void)hipGetLastError();
+        return LC_ELAUNCH;
+    }
+    hipLaunchKernelGGL(kernel, dim3(P_GRID), dim3(P_THREADS), p.lds, s, args);
+    // a shadow the kernel wrote itself (no pass follows it) is poisoned with the fp32 output - a caller of the C ABI that
+    // ignores the status word must not find finite terms of a failed launch
+    const bool shadow = p.shadow == SHADOW_KERNEL;
+    PVerifyArgs va;
+    va.ctl = (PCtl *)workspace; va.nused = 8; va.nwg = p.g.nwg; va.nout = ndir;
+    va.out[0] = dir_out(dirs[0]); va.out[1] = dir_out(dirs[ndir - 1]); va.count = count;
+    // halfwords per shadow: the x3 shadow of dz has three terms (the XCD-pair BPTT says so with or without one)
+    va.count16 = p.bwd && !p.bf16 && (shadow || sched_pair(p.kind)) ? 3 * count : count;
+    va.out16[0] = shadow ? (unsigned short *)dir_shadow(dirs[0]) : nullptr;
+    va.out16[1] = shadow ? (unsigned short *)dir_shadow(dirs[ndir - 1]) : nullptr;
+    hipLaunchKernelGGL(persist_verify_kernel, dim3(256), dim3(256), 0, s, va);
+    LC_CHECK_LAUNCH(what);
+    return LC_OK;
+}
+
+// Folds `nsplit` partial sums of a direction's bias / peephole gradients into (+=) its outputs.
+static void fold_unit_grads(const float *part, int nsplit, int N, const lc_lstm_bwd_dir_t &d, hipStream_t s)
+{
+    hipLaunchKernelGGL(unit_param_fold_kernel, dim3(lc_cdiv(N, 256)), dim3(256), 0, s, part, nsplit, N,
+                       (d.dpeep && d.w_f) ? d.dpeep : nullptr, d.dbias);
+}
+
+// The pass behind a recurrence whose kernel did not write the shadow: hs_bf16 / dz_bf16 as a bf16 cast of hs / dz, or (the
+// split-operand BPTT) dz_bf16 as the x3 shadow of dz ([T * B, 12 N] bf16, lc_split_bf16x3 layout).
+template <class D>
+static int shadow_pass(const Plan &p, const D *dirs, int ndir, int T, int B, int N, lc_stream_t stream)
+{
+    const int cols = p.bwd ? 4 * N : N;
     for (int i = 0; i < ndir; ++i)
-        LC_CHECK_ARG(dirs[i].zx && dirs[i].R && dirs[i].cs && dirs[i].hs, "%s: null pointer in dirs[%d]", who, i);
-    hipStream_t s = (hipStream_t)stream;
-    if (!bf && pair_geom(T, B, N, ndir)) {
-        XFwdArgs xa;
-        for (int i = 0; i < 2; ++i) {
-            const lc_lstm_fwd_dir_t &di = dirs[ndir == 2 ? i : 0];
-            xa.d[i].zx = di.zx; xa.d[i].R = di.R;
-            xa.d[i].w_f = di.w_f; xa.d[i].w_i = di.w_i; xa.d[i].w_o = di.w_o;
-            xa.d[i].cs = di.cs; xa.d[i].hs = di.hs; xa.d[i].hT = nullptr; xa.d[i].reverse = di.reverse;
+        if (dir_shadow(dirs[i])) {
+            const int rc = p.bf16 ? lc_cast_bf16(dir_out(dirs[i]), T * B, cols, cols, dir_shadow(dirs[i]), cols, nullptr, 0, stream)
+                                  : lc_split_bf16x3(dir_out(dirs[i]), T * B, cols, cols, dir_shadow(dirs[i]), 3 * cols, stream);
+            if (rc != LC_OK) return rc;
         }
+    return LC_OK;
+}
+// shadow_only (every direction, each with its shadow): the fp32 hs / dz is not written - the full-width bf16 kernel only
+template <class D>
+static int persist_kernel_row(const Plan &p, const D *dirs, int ndir)
+{
+    bool shonly = p.kernel_shadow_only >= 0;
+    for (int i = 0; i < ndir; ++i) shonly = shonly && dirs[i].shadow_only && dir_shadow(dirs[i]);
+    return shonly ? p.kernel_shadow_only : p.kernel;
+}
+
+// ---- the two walks over the plan -------------------------------------------------------------------------------------
+static int lstm_fwd_walk(bool bf, bool x3, const char *who, const lc_lstm_fwd_dir_t *dirs, int ndir, const int *seq_len, int T,
+                         int B, int N, float forget_bias, void *workspace, size_t workspace_bytes, lc_stream_t stream)
+{
+    const int rc = lstm_check_args(who, false, bf, dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes);
+    if (rc != LC_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Plan p = lstm_plan(false, bf, x3, T, B, N, ndir);
+    const size_t count = (size_t)T * B * N;
+    if (sched_pair(p.kind)) {
+        XFwdArgs xa;
+        for (int i = 0; i < 2; ++i) xa.d[i] = dir_args(dirs[ndir == 2 ? i : 0], false);
         xa.seq_len = seq_len; xa.T = T; xa.B = B; xa.forget_bias = forget_bias;
         xa.spin_limit = persist_spin_limit();
         xa.ctl = (PCtl *)workspace;
         xa.hx = (float *)((char *)workspace + P_CTL_BYTES);
         xa.px = xa.hx + X_HX_FLOATS;
         xa.dbg = g_lstm_dbg;
-        for (int r0 = 0; r0 < B; r0 += pair_rows_per_launch(ndir)) {       // 64-row blocks (per slot), back to back
+        for (int r0 = 0; r0 < B; r0 += p.rows_per_launch) {                // 64-row blocks (per slot), back to back
             xa.row_base[0] = r0;
             xa.row_base[1] = ndir == 2 ? r0 : r0 + 64;                     // (a slot whose block starts past B idles: all rows masked)
-            if (!persist_clear(workspace, pair_fwd_ws_bytes(), s)) {
-                lc_set_error("%s: memset failed", who);
-                return LC_ELAUNCH;
-            }
-            const bool use_x3 = x3 && pair_x3_width(N);
-            const bool launched = use_x3 ? (N == 1024 ? persist_launch(lstm_fwd_pair_x3_kernel<8>, x3_fwd_lds_bytes(8), s, xa)
-                                                      : persist_launch(lstm_fwd_pair_x3_kernel<6>, x3_fwd_lds_bytes(6), s, xa))
-                                : N == 1024 ? persist_launch(lstm_fwd_pair_kernel<8>, (size_t)84 * 1024, s, xa)
-                                : N == 896 ? persist_launch(lstm_fwd_pair_kernel<7>, (size_t)84 * 1024, s, xa)
-                                : N == 768 ? persist_launch(lstm_fwd_pair_kernel<6>, (size_t)84 * 1024, s, xa)
-                                           : persist_launch(lstm_fwd_pair_kernel<5>, (size_t)84 * 1024, s, xa);
-            if (!launched) {
-                lc_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the XCD-pair kernel", who);
-                (void)hipGetLastError();
-                return LC_ELAUNCH;
-            }
-            PVerifyArgs va;
-            va.ctl = xa.ctl; va.nused = 8; va.nwg = N / 32; va.nout = ndir;
-            va.out[0] = dirs[0].hs; va.out[1] = dirs[ndir - 1].hs; va.count = va.count16 = (size_t)T * B * N;
-            va.out16[0] = va.out16[1] = nullptr;
-            hipLaunchKernelGGL(persist_verify_kernel, dim3(256), dim3(256), 0, s, va);
-            LC_CHECK_LAUNCH("lstm_fwd_pair");
+            const int rc2 = persist_run(p, who, "lstm_fwd_pair", XFWD_KERNELS[p.kernel], xa, workspace, dirs, ndir, count, s);
+            if (rc2 != LC_OK) return rc2;
         }
-        g_last_sched = x3 && pair_x3_width(N) ? 6 : 5;
-        return LC_OK;
-    }
-    PFwdArgs pa;
-    size_t lds = 0;
-    const bool persist = bf ? persist_geom_bf16(T, B, N, ndir, pa.g, lds) : persist_geom(T, B, N, ndir, false, pa.g, lds);
-    if (persist) {
-        for (int i = 0; i < ndir; ++i) {
-            pa.d[i].zx = dirs[i].zx; pa.d[i].R = dirs[i].R;
-            pa.d[i].w_f = dirs[i].w_f; pa.d[i].w_i = dirs[i].w_i; pa.d[i].w_o = dirs[i].w_o;
-            pa.d[i].cs = dirs[i].cs; pa.d[i].hs = dirs[i].hs; pa.d[i].hT = nullptr; pa.d[i].reverse = dirs[i].reverse;
-            pa.d[i].hs16 = bf ? dirs[i].hs_bf16 : nullptr;
-        }
-        if (ndir == 1) pa.d[1] = pa.d[0];
-        pa.seq_len = seq_len; pa.forget_bias = forget_bias;
+    } else if (p.kind != SCHED_TRAIN) {
+        PFwdArgs pa;
+        for (int i = 0; i < 2; ++i) pa.d[i] = dir_args(dirs[i < ndir ? i : 0], p.shadow == SHADOW_KERNEL);
+        pa.seq_len = seq_len; pa.g = p.g; pa.forget_bias = forget_bias;
         pa.spin_limit = persist_spin_limit();
         pa.ctl = (PCtl *)workspace;
         pa.hT = (float *)((char *)workspace + P_CTL_BYTES);
         pa.dbg = bf ? nullptr : g_lstm_dbg;
-        if (!persist_clear(workspace, persist_ws_bytes(N, false), s, bf ? 0xff : 0)) {
-            lc_set_error("%s: memset failed", who);
-            return LC_ELAUNCH;
+        const int rc2 = persist_run(p, who, bf ? "lstm_fwd_persist_bf16" : "lstm_fwd_persist", PFWD_KERNELS[persist_kernel_row(p, dirs, ndir)],
+                                    pa, workspace, dirs, ndir, count, s);
+        if (rc2 != LC_OK) return rc2;
+    } else {
+        FwdArgs a;
+        a.seq_len = seq_len; a.T = T; a.B = B; a.N = N; a.Bpad = bpad(B); a.forget_bias = forget_bias;
+        a.dbg = g_lstm_dbg;
+        char *w = (char *)workspace + P_CTL_BYTES;
+        for (int i = 0; i < ndir; ++i) {
+            a.d[i] = dir_args(dirs[i], false);
+            a.d[i].hT = (float *)w;
+            // pad rows of hT (b >= B) are never written by the kernel but are read as MFMA operands
+            if (hipMemsetAsync(w, 0, train_state_bytes(false, B, N), s) != hipSuccess) {
+                lc_set_error("%s: memset failed", who);
+                return LC_ELAUNCH;
+            }
+            w += train_state_bytes(false, B, N);
+            pack_operand(bf, dirs[i].R, N, 4 * N, w, s);
+            a.d[i].R = (const float *)w;
+            w += train_weight_bytes(N);
         }
-        bool ok = false;
-        const bool px3 = !bf && x3 && persist_x3_width(N);
-        if (px3) {                             // split-operand forward kernel: whole 32-blocks per wave, whole tiles per workgroup
-#define LC_PFX(NB) case NB: ok = persist_launch(lstm_fwd_persist_x3_kernel<NB>, lds, s, pa); break;
-            switch (N / 32) { LC_PFX(2) LC_PFX(4) LC_PFX(6) LC_PFX(8) LC_PFX(10) LC_PFX(12) LC_PFX(14) LC_PFX(16) }
-#undef LC_PFX
-        } else if (!bf) {
-            const int per = lc_cdiv(N / 16, NWAVES);
-#define LC_PFWD(PER)                                                                                                   \
-    case PER:                                                                                                          \
-        ok = (N % 64) ? persist_launch(lstm_fwd_persist_kernel<PER, true>, lds, s, pa)                                 \
-                      : persist_launch(lstm_fwd_persist_kernel<PER, false>, lds, s, pa);                               \
-        break;
-            switch (per) { LC_PFWD(1) LC_PFWD(2) LC_PFWD(3) LC_PFWD(4) LC_PFWD(5) LC_PFWD(6) LC_PFWD(7) LC_PFWD(8) }
-#undef LC_PFWD
-        } else {
-            const int perb = lc_cdiv(N / 32, NWAVES);
-#define LC_PFB(PERB, PPT)                                                                                              \
-    case PERB:                                                                                                         \
-        ok = (N % 128) ? persist_launch(lstm_fwd_persist_bf16_kernel<PERB, PPT, true>, lds, s, pa)                     \
-                       : persist_launch(lstm_fwd_persist_bf16_kernel<PERB, PPT, false>, lds, s, pa);                   \
-        break;
-            // shadow_only (every direction, each with its hs_bf16): the fp32 hs is not written - the full-width kernel only
-            bool shonly = N == 1024;
-            for (int i = 0; i < ndir; ++i) shonly = shonly && dirs[i].shadow_only && dirs[i].hs_bf16;
-            if (shonly) ok = persist_launch(lstm_fwd_persist_bf16_kernel<8, 2, false, true>, lds, s, pa);
-            else
-            switch (perb) { LC_PFB(1, 1) LC_PFB(2, 1) LC_PFB(3, 1) LC_PFB(4, 1) LC_PFB(5, 2) LC_PFB(6, 2) LC_PFB(7, 2) LC_PFB(8, 2) }
-#undef LC_PFB
-        }
-        if (!ok) {
-            lc_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the persistent kernel", who);
-            (void)hipGetLastError();
-            return LC_ELAUNCH;
-        }
-        PVerifyArgs va;
-        va.ctl = pa.ctl; va.nused = ndir * pa.g.gpd; va.nwg = pa.g.nwg; va.nout = ndir;
-        va.out[0] = dirs[0].hs; va.out[1] = dirs[ndir - 1].hs; va.count = va.count16 = (size_t)T * B * N;
-        va.out16[0] = bf ? (unsigned short *)dirs[0].hs_bf16 : nullptr;
-        va.out16[1] = bf ? (unsigned short *)dirs[ndir - 1].hs_bf16 : nullptr;
-        hipLaunchKernelGGL(persist_verify_kernel, dim3(256), dim3(256), 0, s, va);
-        LC_CHECK_LAUNCH(bf ? "lstm_fwd_persist_bf16" : "lstm_fwd_persist");
-        g_last_sched = (bf ? 2 : px3 ? 7 : 1) | ((int)bf << 16);
-        return LC_OK;
-    }
-    FwdArgs a;
-    a.seq_len = seq_len; a.T = T; a.B = B; a.N = N; a.Bpad = bpad(B); a.forget_bias = forget_bias;
-    a.dbg = g_lstm_dbg;
-    char *w = (char *)workspace + P_CTL_BYTES;
-    for (int i = 0; i < ndir; ++i) {
-        a.d[i].zx = dirs[i].zx;
-        a.d[i].w_f = dirs[i].w_f; a.d[i].w_i = dirs[i].w_i; a.d[i].w_o = dirs[i].w_o;
-        a.d[i].cs = dirs[i].cs; a.d[i].hs = dirs[i].hs; a.d[i].reverse = dirs[i].reverse;
-        a.d[i].hT = (float *)w;
-        const size_t hbytes = al256((size_t)2 * N * a.Bpad * sizeof(float));
-        // pad rows of hT (b >= B) are never written by the kernel but are read as MFMA operands
-        if (hipMemsetAsync(w, 0, hbytes, s) != hipSuccess) {
-            lc_set_error("%s: memset failed", who);
-            return LC_ELAUNCH;
-        }
-        w += hbytes;
-        pack_operand(bf, dirs[i].R, N, 4 * N, w, s);
-        a.d[i].R = (const float *)w;
-        w += al256((size_t)N * 4 * N * sizeof(float));
-    }
-    if (ndir == 1) a.d[1] = a.d[0];
-    LC_CHECK_LAUNCH("pack_operand");
-    a.row_base = 0;
-    // Two-stream schedule for the big fp32 bidirectional case (c4: N >= 1024, 33..64 rows): one in-order chain of
-    // 32-row-tile launches per direction, the reverse direction on a second stream.  The chains drift apart, so on
-    // every CU one direction's MFMA phase runs under the other's launch boundary / operand latency / gate epilogue:
-    // 13.5 vs 14.8 us per step pair.  Per-row arithmetic is unchanged (same K order), so results are bit-identical.
-    // 57.6 vs 68.5 ms per c4 step.  Not for small steps (two launches per step make N = 320 / 512 host-bound: 8.5 vs
-    // 4.4 us) nor for bf16 (its 8 us step leaves the host < 4 us per launch: the c5 step got 159 vs 153.5 ms).  The second stream is created with HIGH priority so that it can
-    // never share a hardware queue with the caller's stream: two streams on one queue serialise (measured 2x).
-    if (!bf && ndir == 2 && a.Bpad == 64 && N >= 1024) {
+        if (ndir == 1) a.d[1] = a.d[0];
+        LC_CHECK_LAUNCH("pack_operand");
+        a.row_base = 0;
+        // Two-stream schedule for the big fp32 bidirectional case (c4: N >= 1024, 33..64 rows): one in-order chain of
+        // 32-row-tile launches per direction, the reverse direction on a second stream.  The chains drift apart, so on
+        // every CU one direction's MFMA phase runs under the other's launch boundary / operand latency / gate epilogue:
+        // 13.5 vs 14.8 us per step pair.  Per-row arithmetic is unchanged (same K order), so results are bit-identical.
+        // 57.6 vs 68.5 ms per c4 step.  Not for small steps (two launches per step make N = 320 / 512 host-bound: 8.5 vs
+        // 4.4 us) nor for bf16 (its 8 us step leaves the host < 4 us per launch: the c5 step got 159 vs 153.5 ms).  The second stream is created with HIGH priority so that it can
+        // never share a hardware queue with the caller's stream: two streams on one queue serialise (measured 2x).
         hipStream_t s2 = nullptr;
-        DirStreams *ds = dir_streams(s, &s2);
-        if (ds) {
+        DirStreams *ds = p.two_stream ? dir_streams(s, &s2) : nullptr;
+        dim3 grid(N / 8, lc_cdiv(B, 16 * p.mt), ndir);
+        FwdArgs a1 = a;
+        if (ds) {                                  // each chain sees its own direction in both slots, in 32-row tiles
+            p.kind = SCHED_TWO_STREAM;
+            p.mt = 2;
+            grid = dim3(N / 8, lc_cdiv(B, 32), 1);
+            a.d[1] = a.d[0];
+            a1.d[0] = a1.d[1];
+            a1.dbg = nullptr;
             (void)hipEventRecord(ds->fork, s);
             (void)hipStreamWaitEvent(s2, ds->fork, 0);
-            FwdArgs a0 = a, a1 = a;
-            a0.d[1] = a0.d[0];
-            a1.d[0] = a.d[1];
-            a1.dbg = nullptr;
-            dim3 g1(N / 8, lc_cdiv(B, 32), 1);
-            for (int step = 0; step < T; ++step) {
-                a0.step = a1.step = step;
-                launch_fwd_step<false>(2, g1, s, a0);
-                launch_fwd_step<false>(2, g1, s2, a1);
-            }
+        }
+        for (int step = 0; step < T; ++step) {
+            a.step = a1.step = step;
+            hipLaunchKernelGGL(FWD_STEP_KERNELS[both(p.mt - 1, bf)], grid, dim3(NTHREADS), 0, s, a);
+            if (ds) hipLaunchKernelGGL(FWD_STEP_KERNELS[both(p.mt - 1, bf)], grid, dim3(NTHREADS), 0, s2, a1);
+        }
+        if (ds) {
             (void)hipEventRecord(ds->join, s2);
             (void)hipStreamWaitEvent(s, ds->join, 0);
-            LC_CHECK_LAUNCH("lstm_fwd_step");
-            g_last_sched = 3 | (2 << 8);
-            return LC_OK;
         }
+        LC_CHECK_LAUNCH("lstm_fwd_step");
     }
-    // Row tile: 64 rows per workgroup when that already fills the chip (N = 1024: 256 workgroups; more, smaller
-    // tiles re-stream R and measured 18.5 vs 15.1 us), halved while the grid would leave CUs idle (N = 320 / 512 at
-    // B = 32: 5.4 -> 4.7 and 6.3 -> 5.3 us per step).
-    int mt = a.Bpad >= 64 ? 4 : a.Bpad / 16;
-    while (mt > 1 && (long long)(N / 8) * lc_cdiv(B, 16 * mt) * ndir < 200) mt = (mt + 1) / 2;
-    dim3 grid(N / 8, lc_cdiv(B, 16 * mt), ndir);
-    for (int step = 0; step < T; ++step) {
-        a.step = step;
-        if (bf) launch_fwd_step<true>(mt, grid, s, a);
-        else launch_fwd_step<false>(mt, grid, s, a);
-    }
-    LC_CHECK_LAUNCH("lstm_fwd_step");
-    g_last_sched = 4 | (mt << 8) | ((int)bf << 16);
-    return LC_OK;
+    g_last_sched = sched_word(p, false);
+    return p.shadow == SHADOW_PASS ? shadow_pass(p, dirs, ndir, T, B, N, stream) : LC_OK;
 }
 
-static int lstm_bwd_impl(bool bf, bool x3, const char *who, const lc_lstm_bwd_dir_t *dirs, int ndir, const int *seq_len, int T,
+static int lstm_bwd_walk(bool bf, bool x3, const char *who, const lc_lstm_bwd_dir_t *dirs, int ndir, const int *seq_len, int T,
                          int B, int N, void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    LC_CHECK_ARG(dirs && seq_len && workspace, "%s: null pointer", who);
-    LC_CHECK_ARG(ndir == 1 || ndir == 2, "%s: ndir must be 1 or 2", who);
-    LC_CHECK_ARG(T > 0 && B > 0 && N > 0 && N % (bf ? 32 : 16) == 0, "%s: need T,B > 0 and num_neurons %% %d == 0 (N=%d)",
-                 who, bf ? 32 : 16, N);
-    if (workspace_bytes < lc_lstm_bwd_workspace_bytes(B, N, ndir)) {
-        lc_set_error("%s: workspace too small", who);
-        return LC_EWORKSPACE;
-    }
-    for (int i = 0; i < ndir; ++i)
-        LC_CHECK_ARG(dirs[i].gates && dirs[i].RT && dirs[i].cs && dirs[i].dh, "%s: null pointer in dirs[%d]", who, i);
+    const int rc = lstm_check_args(who, true, bf, dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes);
+    if (rc != LC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    float *upg_part = (float *)((char *)workspace + lstm_bwd_main_bytes(B, N, ndir));
-    PBwdArgs pa;
-    size_t plds = 0;
-    const bool pair = !bf && pair_geom(T, B, N, ndir);
-    const bool persist = !pair && (bf ? persist_geom_bf16(T, B, N, ndir, pa.g, plds) : persist_geom(T, B, N, ndir, true, pa.g, plds));
-    if (pair) {
+    float *upg_part = (float *)((char *)workspace + lstm_main_bytes(true, B, N, ndir));
+    const Plan p = lstm_plan(true, bf, x3, T, B, N, ndir);
+    const size_t count = (size_t)T * B * 4 * N;
+    const bool shadow = p.shadow == SHADOW_KERNEL;
+    // ... and no pass follows it (the x3 shadow: when direction 0 has one; then bit 18 of the schedule word says so)
+    const bool shadow_done = shadow && (bf || dirs[0].dz_bf16);
+    const bool x3_shadow_written = shadow_done && !bf;
+    if (sched_pair(p.kind)) {
         XBwdArgs xa;
         for (int i = 0; i < 2; ++i) {
             const lc_lstm_bwd_dir_t &di = dirs[ndir == 2 ? i : 0];
-            xa.d[i].gates = di.gates; xa.d[i].RT = di.RT;
-            xa.d[i].w_f = di.w_f; xa.d[i].w_i = di.w_i; xa.d[i].w_o = di.w_o;
-            xa.d[i].cs = di.cs; xa.d[i].dh = di.dh; xa.d[i].dc = nullptr; xa.d[i].dzT = nullptr;
-            xa.d[i].reverse = di.reverse;
-            // split-operand kernel: the x3 shadow of dz (lc_lstm_bwd_x3), written by the producers that split dz anyway -
-            // while its byte offsets fit the 32-bit buffer addressing of the kernel
-            xa.d[i].dz16 = (x3 && pair_x3_width(N) && (unsigned long long)T * B * 12 * N * 2 <= 0x7fffffffull) ? di.dz_bf16 : nullptr;
+            xa.d[i] = dir_args(di, shadow);
+            xa.upg[i] = wants_unit_grads(di) ? upg_part + (size_t)i * UPG_SPLITS * 7 * N : nullptr;
         }
         xa.seq_len = seq_len; xa.T = T; xa.B = B;
         xa.spin_limit = persist_spin_limit();
         xa.ctl = (PCtl *)workspace;
-        const bool use_x3 = x3 && pair_x3_width(N);
         xa.dzx = (float *)((char *)workspace + P_CTL_BYTES);
-        xa.px = xa.dzx + (use_x3 ? X3B_DZX_FLOATS : XB_DZX_FLOATS);
-        for (int i = 0; i < 2; ++i) {
-            const lc_lstm_bwd_dir_t &di = dirs[ndir == 2 ? i : 0];
-            const bool want = (di.dpeep && di.w_f) || di.dbias;
-            xa.upg[i] = want ? upg_part + (size_t)i * UPG_SPLITS * 7 * N : nullptr;
-        }
+        xa.px = xa.dzx + (p.split ? X3B_DZX_FLOATS : XB_DZX_FLOATS);
         xa.dbg = g_lstm_dbg;
-        for (int r0 = 0; r0 < B; r0 += pair_rows_per_launch(ndir)) {       // 64-row blocks (per slot), back to back
+        for (int r0 = 0; r0 < B; r0 += p.rows_per_launch) {                // 64-row blocks (per slot), back to back
             xa.row_base[0] = r0;
             xa.row_base[1] = ndir == 2 ? r0 : r0 + 64;
-            if (!persist_clear(workspace, use_x3 ? pair_bwd_x3_ws_bytes() : pair_bwd_ws_bytes(), s)) {
-                lc_set_error("%s: memset failed", who);
-                return LC_ELAUNCH;
-            }
-            const bool launched = use_x3 ? (N == 1024 ? persist_launch(lstm_bwd_pair_x3_kernel<8>, x3_bwd_lds_bytes(8), s, xa)
-                                                      : persist_launch(lstm_bwd_pair_x3_kernel<6>, x3_bwd_lds_bytes(6), s, xa))
-                                : N == 1024 ? persist_launch(lstm_bwd_pair_kernel<8>, (size_t)84 * 1024, s, xa)
-                                : N == 896 ? persist_launch(lstm_bwd_pair_kernel<7>, (size_t)84 * 1024, s, xa)
-                                : N == 768 ? persist_launch(lstm_bwd_pair_kernel<6>, (size_t)84 * 1024, s, xa)
-                                           : persist_launch(lstm_bwd_pair_kernel<5>, (size_t)84 * 1024, s, xa);
-            if (!launched) {
-                lc_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the XCD-pair kernel", who);
-                (void)hipGetLastError();
-                return LC_ELAUNCH;
-            }
-            PVerifyArgs va;
-            va.ctl = xa.ctl; va.nused = 8; va.nwg = N / 32; va.nout = ndir;
-            va.out[0] = dirs[0].gates; va.out[1] = dirs[ndir - 1].gates; va.count = (size_t)T * B * 4 * N;
-            // the x3 shadow the producers wrote themselves (no split pass follows it: schedule-word bit 18) is poisoned with
-            // the fp32 dz - a caller of the C ABI that ignores the status word must not find finite terms of a failed launch
-            va.count16 = 3 * va.count;
-            va.out16[0] = (unsigned short *)xa.d[0].dz16; va.out16[1] = (unsigned short *)xa.d[ndir - 1].dz16;
-            hipLaunchKernelGGL(persist_verify_kernel, dim3(256), dim3(256), 0, s, va);
-            LC_CHECK_LAUNCH("lstm_bwd_pair");
+            const int rc2 = persist_run(p, who, "lstm_bwd_pair", XBWD_KERNELS[p.kernel], xa, workspace, dirs, ndir, count, s);
+            if (rc2 != LC_OK) return rc2;
             // the kernel left the block's per-row partials of the bias / peephole gradients: fold them into (+=) the outputs
-            for (int i = 0; i < 2; ++i) {
-                const lc_lstm_bwd_dir_t &di = dirs[ndir == 2 ? i : 0];
-                if (xa.upg[i])
-                    hipLaunchKernelGGL(unit_param_fold_kernel, dim3(lc_cdiv(N, 256)), dim3(256), 0, s, xa.upg[i], UPG_SPLITS, N,
-                                       (di.dpeep && di.w_f) ? di.dpeep : nullptr, di.dbias);
-            }
+            for (int i = 0; i < 2; ++i)
+                if (xa.upg[i]) fold_unit_grads(xa.upg[i], UPG_SPLITS, N, dirs[ndir == 2 ? i : 0], s);
             LC_CHECK_LAUNCH("unit_param_fold");
         }
-        g_last_sched = (x3 && pair_x3_width(N) ? 6 : 5) | (1 << 17) | ((xa.d[0].dz16 ? 1 : 0) << 18);
-        return LC_OK;
-    } else if (persist) {
-        for (int i = 0; i < ndir; ++i) {
-            pa.d[i].gates = dirs[i].gates; pa.d[i].RT = dirs[i].RT;
-            pa.d[i].w_f = dirs[i].w_f; pa.d[i].w_i = dirs[i].w_i; pa.d[i].w_o = dirs[i].w_o;
-            pa.d[i].cs = dirs[i].cs; pa.d[i].dh = dirs[i].dh; pa.d[i].dc = nullptr; pa.d[i].dzT = nullptr;
-            pa.d[i].dz16 = bf ? dirs[i].dz_bf16 : nullptr;
-            pa.d[i].reverse = dirs[i].reverse;
+        g_last_sched = sched_word(p, x3_shadow_written);
+    } else if (p.kind != SCHED_TRAIN) {
+        PBwdArgs pa;
+        for (int i = 0; i < 2; ++i) {            // per-row partial bias / peephole gradients: [B][7][N] per direction
+            const int j = i < ndir ? i : 0;
+            pa.d[i] = dir_args(dirs[j], shadow);
+            pa.upg[i] = wants_unit_grads(dirs[j]) ? upg_part + (size_t)j * B * 7 * N : nullptr;
         }
-        // split-operand kernel: dz_bf16 is the x3 shadow of dz (lc_lstm_bwd_x3), written by the producers that split dz anyway -
-        // while its byte offsets fit the 32-bit buffer addressing of the kernel
-        const bool px3 = !bf && x3 && persist_x3_width(N);
-        const bool shadow3 = px3 && (unsigned long long)T * B * 12 * N * 2 <= 0x7fffffffull;
-        if (shadow3)
-            for (int i = 0; i < ndir; ++i) pa.d[i].dz16 = (unsigned short *)dirs[i].dz_bf16;
-        if (ndir == 1) pa.d[1] = pa.d[0];
-        pa.seq_len = seq_len;
+        pa.seq_len = seq_len; pa.g = p.g;
         pa.spin_limit = persist_spin_limit();
         pa.ctl = (PCtl *)workspace;
         pa.dzT = (float *)((char *)workspace + P_CTL_BYTES);
-        for (int i = 0; i < 2; ++i) {            // per-row partial bias / peephole gradients: [B][7][N] per direction
-            const bool want = i < ndir && ((dirs[i].dpeep && dirs[i].w_f) || dirs[i].dbias);
-            pa.upg[i] = want ? upg_part + (size_t)i * B * 7 * N : nullptr;
-        }
-        if (ndir == 1) pa.upg[1] = pa.upg[0];
         pa.dbg = g_lstm_dbg;
-        if (!persist_clear(workspace, px3 ? persist_bwd_x3_ws_bytes(N) : persist_ws_bytes(N, true), s, bf ? 0xff : 0)) {
-            lc_set_error("%s: memset failed", who);
-            return LC_ELAUNCH;
-        }
-        bool ok = false;
-        if (px3) {                              // split-operand BPTT: the producers split, pieces of 32-blocks
-#define LC_PBX(NBW) case NBW: ok = persist_launch(lstm_bwd_persist_x3_kernel<NBW>, plds, s, pa); break;
-            switch (N / 32) { LC_PBX(2) LC_PBX(4) LC_PBX(6) LC_PBX(8) LC_PBX(10) LC_PBX(12) LC_PBX(14) LC_PBX(16) }
-#undef LC_PBX
-        } else if (bf) {
-            const int nch = lc_cdiv(N, 256);
-#define LC_PBB(NCH, PPT)                                                                                               \
-    case NCH:                                                                                                          \
-        ok = (N % 256) ? persist_launch(lstm_bwd_persist_bf16_kernel<NCH, PPT, true>, plds, s, pa)                     \
-                       : persist_launch(lstm_bwd_persist_bf16_kernel<NCH, PPT, false>, plds, s, pa);                   \
-        break;
-            bool shonly = N == 1024;            // shadow_only: the fp32 dz is not written (see lc_lstm_fwd_bf16)
-            for (int i = 0; i < ndir; ++i) shonly = shonly && dirs[i].shadow_only && dirs[i].dz_bf16;
-            if (shonly) ok = persist_launch(lstm_bwd_persist_bf16_kernel<4, 2, false, true>, plds, s, pa);
-            else
-            switch (nch) { LC_PBB(1, 1) LC_PBB(2, 1) LC_PBB(3, 2) LC_PBB(4, 2) }
-#undef LC_PBB
-        } else {
-            const int nq = lc_cdiv(lc_cdiv(4 * N / 16, NWAVES), 4);
-#define LC_PBWD(NQ)                                                                                                    \
-    case NQ:                                                                                                           \
-        ok = (N % 64) ? persist_launch(lstm_bwd_persist_kernel<NQ, true>, plds, s, pa)                                 \
-                      : persist_launch(lstm_bwd_persist_kernel<NQ, false>, plds, s, pa);                               \
-        break;
-            switch (nq) { LC_PBWD(1) LC_PBWD(2) LC_PBWD(3) LC_PBWD(4) LC_PBWD(5) LC_PBWD(6) LC_PBWD(7) LC_PBWD(8) }
-#undef LC_PBWD
-        }
-        if (!ok) {
-            lc_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the persistent kernel", who);
-            (void)hipGetLastError();
-            return LC_ELAUNCH;
-        }
-        PVerifyArgs va;
-        va.ctl = pa.ctl; va.nused = ndir * pa.g.gpd; va.nwg = pa.g.nwg; va.nout = ndir;
-        va.out[0] = dirs[0].gates; va.out[1] = dirs[ndir - 1].gates; va.count = (size_t)T * B * 4 * N;
-        va.count16 = shadow3 ? 3 * va.count : va.count;      // split-operand kernel: the x3 shadow of dz its producers wrote
-        va.out16[0] = (bf || shadow3) ? (unsigned short *)dirs[0].dz_bf16 : nullptr;
-        va.out16[1] = (bf || shadow3) ? (unsigned short *)dirs[ndir - 1].dz_bf16 : nullptr;
-        hipLaunchKernelGGL(persist_verify_kernel, dim3(256), dim3(256), 0, s, va);
-        LC_CHECK_LAUNCH("lstm_bwd_persist");
-        g_last_sched = (bf ? 2 : px3 ? 7 : 1) | ((int)bf << 16) | (1 << 17) | ((shadow3 && dirs[0].dz_bf16 ? 1 : 0) << 18);
+        const int rc2 = persist_run(p, who, "lstm_bwd_persist", PBWD_KERNELS[persist_kernel_row(p, dirs, ndir)], pa, workspace, dirs, ndir,
+                                    count, s);
+        if (rc2 != LC_OK) return rc2;
+        g_last_sched = sched_word(p, x3_shadow_written);
         for (int i = 0; i < ndir; ++i)           // the kernel left per-row partials ([B][7][N]): only the fold remains
-            if (pa.upg[i])
-                hipLaunchKernelGGL(unit_param_fold_kernel, dim3(lc_cdiv(N, 256)), dim3(256), 0, s, pa.upg[i], B, N,
-                                   (dirs[i].dpeep && dirs[i].w_f) ? dirs[i].dpeep : nullptr, dirs[i].dbias);
+            if (pa.upg[i]) fold_unit_grads(pa.upg[i], B, N, dirs[i], s);
         LC_CHECK_LAUNCH("unit_param_fold");
-        return LC_OK;
     } else {
         BwdArgs a;
         a.seq_len = seq_len; a.T = T; a.B = B; a.N = N; a.Bpad = bpad(B); a.row_base = 0;
         char *w = (char *)workspace + P_CTL_BYTES;
         for (int i = 0; i < ndir; ++i) {
-            a.d[i].gates = dirs[i].gates;
-            a.d[i].w_f = dirs[i].w_f; a.d[i].w_i = dirs[i].w_i; a.d[i].w_o = dirs[i].w_o;
-            a.d[i].cs = dirs[i].cs; a.d[i].dh = dirs[i].dh; a.d[i].reverse = dirs[i].reverse;
-            const size_t zbytes = al256((size_t)2 * 4 * N * a.Bpad * sizeof(float)) + al256((size_t)B * N * sizeof(float));
-            if (hipMemsetAsync(w, 0, zbytes, s) != hipSuccess) {
+            a.d[i] = dir_args(dirs[i], false);
+            if (hipMemsetAsync(w, 0, train_state_bytes(true, B, N), s) != hipSuccess) {
                 lc_set_error("%s: memset failed", who);
                 return LC_ELAUNCH;
             }
-            a.d[i].dzT = (float *)w; w += al256((size_t)2 * 4 * N * a.Bpad * sizeof(float));
-            a.d[i].dc = (float *)w; w += al256((size_t)B * N * sizeof(float));
+            a.d[i].dzT = (float *)w;
+            a.d[i].dc = (float *)(w + train_pingpong_bytes(true, B, N));
+            w += train_state_bytes(true, B, N);
             pack_operand(bf, dirs[i].RT, 4 * N, N, w, s);
             a.d[i].RT = (const float *)w;
-            w += al256((size_t)N * 4 * N * sizeof(float));
+            w += train_weight_bytes(N);
         }
         if (ndir == 1) a.d[1] = a.d[0];
         LC_CHECK_LAUNCH("pack_operand");
-        // 32-row tiles: (N/16) x (B/32) x ndir workgroups of [32 x 16] outputs - 256 of them at N=1024, B=64
-        // ... and 16-row tiles when that grid would leave most of the 256 CUs idle (N = 320 / 512 at B = 32: 40 / 64
-        // workgroups -> 80 / 128; measured 7.4 -> 5.9 and 9.2 -> 7.0 us per step)
-        int mt = a.Bpad >= 32 ? 2 : 1;
-        if ((long long)(N / 16) * lc_cdiv(B, 32) * ndir < 200) mt = 1;
-        dim3 grid(N / 16, lc_cdiv(B, 16 * mt), ndir), block(NTHREADS);
         // (the two-stream schedule of the forward pass does not pay here: 81-92 vs 80 ms per c4 step - the BPTT step
         // moves twice the operand bytes through L2 and gains nothing from interleaving)
+        const dim3 grid(N / 16, lc_cdiv(B, 16 * p.mt), ndir);
         for (int step = 0; step < T; ++step) {
             a.step = step;
-            if (bf) {
-                if (mt == 1) hipLaunchKernelGGL((lstm_bwd_step_kernel<1, true>), grid, block, 0, s, a);
-                else hipLaunchKernelGGL((lstm_bwd_step_kernel<2, true>), grid, block, 0, s, a);
-            } else {
-                if (mt == 1) hipLaunchKernelGGL((lstm_bwd_step_kernel<1, false>), grid, block, 0, s, a);
-                else hipLaunchKernelGGL((lstm_bwd_step_kernel<2, false>), grid, block, 0, s, a);
-            }
+            hipLaunchKernelGGL(BWD_STEP_KERNELS[both(p.mt - 1, bf)], grid, dim3(NTHREADS), 0, s, a);
         }
         LC_CHECK_LAUNCH("lstm_bwd_step");
-        g_last_sched = 4 | (mt << 8) | ((int)bf << 16) | (1 << 17);
+        g_last_sched = sched_word(p, false);
+        // bias and peephole gradients (batched, f32, one pass over dz, deterministic two-stage reduce)
+        for (int i = 0; i < ndir; ++i)
+            if (wants_unit_grads(dirs[i])) {
+                hipLaunchKernelGGL(unit_param_grad_kernel, dim3(lc_cdiv(N, 64), UPG_SPLITS), dim3(256), 0, s, dirs[i].gates, dirs[i].cs,
+                                   T, B, N, dirs[i].reverse, (dirs[i].dpeep && dirs[i].w_f) ? 1 : 0, upg_part);
+                fold_unit_grads(upg_part, UPG_SPLITS, N, dirs[i], s);
+            }
+        LC_CHECK_LAUNCH("unit_param_grad");
     }
-    // bias and peephole gradients (batched, f32, one pass over dz, deterministic two-stage reduce)
-    for (int i = 0; i < ndir; ++i) {
-        float *dpeep = (dirs[i].dpeep && dirs[i].w_f) ? dirs[i].dpeep : nullptr;
-        if (dpeep || dirs[i].dbias) {
-            dim3 g2(lc_cdiv(N, 64), UPG_SPLITS);
-            hipLaunchKernelGGL(unit_param_grad_kernel, g2, dim3(256), 0, s, dirs[i].gates, dirs[i].cs, T, B, N,
-                               dirs[i].reverse, dpeep ? 1 : 0, upg_part);
-            hipLaunchKernelGGL(unit_param_fold_kernel, dim3(lc_cdiv(N, 256)), dim3(256), 0, s, upg_part, UPG_SPLITS, N,
-                               dpeep, dirs[i].dbias);
-        }
-    }
-    LC_CHECK_LAUNCH("unit_param_grad");
-    return LC_OK;
+    return p.shadow != SHADOW_NONE && !shadow_done ? shadow_pass(p, dirs, ndir, T, B, N, stream) : LC_OK;
 }
 
 extern "C" int lc_lstm_fwd(const lc_lstm_fwd_dir_t *dirs, int ndir, const int *seq_len, int T, int B, int N,
                            float forget_bias, void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    return lstm_fwd_impl(false, false, "lc_lstm_fwd", dirs, ndir, seq_len, T, B, N, forget_bias, workspace, workspace_bytes, stream);
+    return lstm_fwd_walk(false, false, "lc_lstm_fwd", dirs, ndir, seq_len, T, B, N, forget_bias, workspace, workspace_bytes, stream);
 }
 extern "C" int lc_lstm_fwd_x3(const lc_lstm_fwd_dir_t *dirs, int ndir, const int *seq_len, int T, int B, int N,
                               float forget_bias, void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    return lstm_fwd_impl(false, true, "lc_lstm_fwd_x3", dirs, ndir, seq_len, T, B, N, forget_bias, workspace, workspace_bytes, stream);
+    return lstm_fwd_walk(false, true, "lc_lstm_fwd_x3", dirs, ndir, seq_len, T, B, N, forget_bias, workspace, workspace_bytes, stream);
 }
 extern "C" int lc_lstm_fwd_bf16(const lc_lstm_fwd_dir_t *dirs, int ndir, const int *seq_len, int T, int B, int N,
                                 float forget_bias, void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    const int rc = lstm_fwd_impl(true, false, "lc_lstm_fwd_bf16", dirs, ndir, seq_len, T, B, N, forget_bias, workspace, workspace_bytes, stream);
-    if (rc != LC_OK || T <= 0 || B <= 0) return rc;
-    // hs_bf16: the persistent kernel writes it next to hs; every other schedule gets a cast behind the recurrence
-    if ((lc_debug_last_lstm_schedule() & 0xff) != 2)
-        for (int i = 0; i < ndir; ++i)
-            if (dirs[i].hs_bf16) {
-                const int rc2 = lc_cast_bf16(dirs[i].hs, T * B, N, N, dirs[i].hs_bf16, N, nullptr, 0, stream);
-                if (rc2 != LC_OK) return rc2;
-            }
-    return LC_OK;
+    return lstm_fwd_walk(true, false, "lc_lstm_fwd_bf16", dirs, ndir, seq_len, T, B, N, forget_bias, workspace, workspace_bytes, stream);
 }
 extern "C" int lc_lstm_bwd(const lc_lstm_bwd_dir_t *dirs, int ndir, const int *seq_len, int T, int B, int N,
                            void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    return lstm_bwd_impl(false, false, "lc_lstm_bwd", dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes, stream);
+    return lstm_bwd_walk(false, false, "lc_lstm_bwd", dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes, stream);
 }
 extern "C" int lc_lstm_bwd_x3(const lc_lstm_bwd_dir_t *dirs, int ndir, const int *seq_len, int T, int B, int N,
                               void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    const int rc = lstm_bwd_impl(false, true, "lc_lstm_bwd_x3", dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes, stream);
-    if (rc != LC_OK || T <= 0 || B <= 0) return rc;
-    // dz_bf16 here = the x3 shadow of dz ([T * B, 12 N] bf16, lc_split_bf16x3 layout): written by the split-operand pair
-    // kernel's producers (bit 18 of the schedule word); every other schedule gets the split pass behind the recurrence
-    if (!((lc_debug_last_lstm_schedule() >> 18) & 1))
-        for (int i = 0; i < ndir; ++i)
-            if (dirs[i].dz_bf16) {
-                const int rc2 = lc_split_bf16x3(dirs[i].gates, T * B, 4 * N, 4 * N, dirs[i].dz_bf16, 12 * N, stream);
-                if (rc2 != LC_OK) return rc2;
-            }
-    return LC_OK;
+    return lstm_bwd_walk(false, true, "lc_lstm_bwd_x3", dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes, stream);
 }
 extern "C" int lc_lstm_bwd_bf16(const lc_lstm_bwd_dir_t *dirs, int ndir, const int *seq_len, int T, int B, int N,
                                 void *workspace, size_t workspace_bytes, lc_stream_t stream)
 {
-    const int rc = lstm_bwd_impl(true, false, "lc_lstm_bwd_bf16", dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes, stream);
-    if (rc != LC_OK || T <= 0 || B <= 0) return rc;
-    if ((lc_debug_last_lstm_schedule() & 0xff) != 2)        // see lc_lstm_fwd_bf16
-        for (int i = 0; i < ndir; ++i)
-            if (dirs[i].dz_bf16) {
-                const int rc2 = lc_cast_bf16(dirs[i].gates, T * B, 4 * N, 4 * N, dirs[i].dz_bf16, 4 * N, nullptr, 0, stream);
-                if (rc2 != LC_OK) return rc2;
-            }
-    return LC_OK;
+    return lstm_bwd_walk(true, false, "lc_lstm_bwd_bf16", dirs, ndir, seq_len, T, B, N, workspace, workspace_bytes, stream);
 }
+

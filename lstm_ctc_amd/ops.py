@@ -116,13 +116,17 @@ class force_launch_train:
             set_option("lstm_persistent", None)
 
 
-def last_lstm_schedule():
-    """Decoded lc_debug_last_lstm_schedule(): dict(kind, mt, bf16, backward)."""
-    v = _lib.load().lc_debug_last_lstm_schedule()
+def decode_lstm_schedule(v):
+    """The schedule word of lc_debug_last_lstm_schedule() as dict(kind, mt, bf16, backward, dz_shadow_in_kernel)."""
     kinds = {0: "none", 1: "persistent_f32", 2: "persistent_bf16", 3: "two_stream_train", 4: "launch_train",
              5: "persistent_f32_xcd_pair", 6: "persistent_x3_xcd_pair", 7: "persistent_x3"}
     return dict(kind=kinds.get(v & 0xff, "?"), mt=(v >> 8) & 0xff, bf16=bool(v >> 16 & 1), backward=bool(v >> 17 & 1),
                 dz_shadow_in_kernel=bool(v >> 18 & 1))
+
+
+def last_lstm_schedule():
+    """Decoded lc_debug_last_lstm_schedule() of this thread's last accepted lc_lstm_* call."""
+    return decode_lstm_schedule(_lib.load().lc_debug_last_lstm_schedule())
 
 
 def last_ctc_path():

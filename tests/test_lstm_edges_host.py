@@ -12,7 +12,8 @@ that a bf16 recurrence can be checked step by step without a rounding-boundary f
 ``test_reference_agrees_with_the_c_oracle`` anchors both against oracle.lstmp_fwd / lstmp_bwd (kernel = [identity; R], bias 0,
 no projection: the oracle's gates / cs / mp / dx are the op's gates / cs / hs / dz) at < 1e-12.
 
-Dispatch, restated from lstm_fwd_impl / lstm_bwd_impl and the header (``expected``), in this order:
+Dispatch, restated from lstm_plan / lstm_fwd_walk and the header (``expected``; test_lstm_dispatch_host.py holds it to the C
+rule on the CPU), in this order:
 
     XCD-pair schedule (5; 6 = split-operand at N = 768 / 1024): fp32 and split-operand entries, N in {640, 768, 896, 1024},
         T >= 4, T * B * 4N * 4 < 2^32
