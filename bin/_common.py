@@ -368,6 +368,42 @@ def report_row_conv(nnet_config):
         tflog.info(line)
 
 
+def report_time_reduce(nnet_config, args=None, aligning=False):
+    """One INFO line when <nnet-config> sets time_reduce_layers (the pyramidal BiLSTM): the layers, r, R and how
+    many model and raw frames one frame of the logits stands for.  A config the model refuses, or (``args``) a command line
+    that brings a table at the input's frame rate - --frame-targets / --align-window, --teacher-scores, --objective xent|kd -:
+    the FATAL line and exit 1, before a model is built."""
+    from lstm_ctc_amd.nnet.model import time_reduce_info_line
+    try:
+        line = time_reduce_info_line(nnet_config)
+    except ValueError as exc:
+        _fatal(str(exc))
+    if not line:
+        return
+    tabled = [flag for flag, on in (('--frame-targets', getattr(args, 'frame_targets', None)),
+                                    ('--align-window', getattr(args, 'align_window', None) is not None),
+                                    ('--teacher-scores', getattr(args, 'teacher_scores', None)),
+                                    ('--objective %s' % getattr(args, 'objective', 'ctc'),
+                                     getattr(args, 'objective', 'ctc') not in (None, 'ctc'))) if on]
+    if aligning:
+        _fatal('time_reduce_layers does not combine with alignment: an alignment names a symbol per input frame, the logits '
+               'come once per several of them')
+    if tabled:
+        _fatal('time_reduce_layers does not combine with %s: its table is at the input\'s frame rate, the logits are not '
+               '(re-timed tables are not built)' % ', '.join(tabled))
+    from lstm_ctc_amd.nnet import tflog
+    tflog.info(line)
+
+
+def report_time_reduce_short(graph):
+    """One INFO line at the end of a pass of a pyramidal model: the utterances whose labels, with a blank between adjacent
+    repeats, needed more frames than the logits had left (the criterion skips them or finds no path)."""
+    if getattr(graph.model, 'time_factor', 1) > 1:
+        from lstm_ctc_amd.nnet import tflog
+        tflog.info('time reduction by %d: %d utterance(s) whose labels and adjacent repeats no longer fit their output frames'
+                   % (graph.model.time_factor, graph.time_reduce_short))
+
+
 def quiet_unless_rank0(rank):
     """Only rank 0 emits the machine-parsed log lines (scripts/train.sh greps one tr_loss / cv_loss line)."""
     if rank != 0:

@@ -685,6 +685,29 @@ int lc_row_conv_bwd(const float *x, int ldx, const float *dy, int lddy, const fl
                     const int *seq_len, float *dx /* or NULL */, int lddx, float *dw /* or NULL */, void *workspace,
                     size_t workspace_bytes, lc_stream_t stream);
 
+/* ------------------------------------------------------------------ time reduction ---------- */
+/* The layout passes of the pyramidal BiLSTM (Chan et al. 2016, "Listen, Attend and Spell"; no reference counterpart; DESIGN.md
+ * 3.17): r consecutive frames of a layer's output become one frame, r times as wide, of the next layer's input, which then
+ * runs on To = ceil(T / r) frames.  x and dx are time-major [T * B, C] with row pitches ldx / lddx in floats, y and dy are
+ * time-major [To * B, r * C] with row pitches ldy / lddy (column windows of wider buffers are fine); seq_len is a device [B]
+ * int32 and is REQUIRED.  With len_b = clamp(seq_len[b], 0, T):
+ *   lc_time_reduce_fwd   y[to, b, j * C + c] = x[r * to + j, b, c]            if r * to + j < len_b, else +0, for j < r
+ *   lc_time_reduce_bwd   dx[t, b, c]         = dy[t / r, b, (t % r) * C + c]  if t < len_b, else +0
+ *   - Full writes: every element of the output window ([To * B, r * C] of y, [T * B, C] of dx) is written on every successful
+ *     call (no memset needed), and nothing outside the window is touched.  A last group that T or the utterance's end cuts
+ *     short is filled with +0.
+ *   - Copies are bit exact.  A dead source frame is never read: a NaN in a frame at or past len_b, or in a pad column beyond a
+ *     window, has no effect.
+ *   - A pure function of its arguments (no atomics): the same call gives the same bits.
+ *   - Elements are indexed in 64 bits.  16-byte accesses when C and both pitches are multiples of 4 and both bases 16-byte
+ *     aligned, a scalar path otherwise.
+ * LC_EINVAL, with nothing launched and no output touched: T, B, C <= 0; r < 2 or r > 4; a NULL pointer; ldx / lddx below C or
+ * ldy / lddy below r * C; input and output windows whose byte ranges overlap. */
+int lc_time_reduce_fwd(const float *x, int ldx, int T, int B, int C, int r, const int *seq_len, float *y, int ldy,
+                       lc_stream_t stream);
+int lc_time_reduce_bwd(const float *dy, int lddy, int T, int B, int C, int r, const int *seq_len, float *dx, int lddx,
+                       lc_stream_t stream);
+
 /* ------------------------------------------------------------------ SpecAugment ------------- */
 /* Time and frequency masking of the filterbank input (Park et al., 2019; no reference counterpart), on the spliced and
  * subsampled batch the loader uploads.  x and out are time-major [T * B, D] with row pitches ldx / ldo (floats); out == x (in

@@ -91,6 +91,8 @@ SIGNATURES = {
     "lc_row_conv_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "lc_row_conv_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lc_time_reduce_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "lc_time_reduce_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "lc_spec_augment": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_u32, c_void_p, c_int, c_void_p,
                                 c_void_p]),
     "lc_lstm_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

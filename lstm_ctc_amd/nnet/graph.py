@@ -20,7 +20,7 @@ import torch
 
 from .. import ops
 from . import dp
-from .model import Model, config_keep
+from .model import Model, config_keep, time_reduce_config
 
 
 class OutOfRangeError(Exception):
@@ -385,7 +385,17 @@ class CTCGraph:
         self.cr_loss_total, self.cr_frames_total, self.cr_agree_total = 0.0, 0, 0
         self.specaug_frames_masked = self.specaug_frames = self.specaug_bins_masked = self.specaug_bins = 0
         self.pipeline = pipeline
+        # pyramidal BiLSTM (time_reduce_layers): the logits come at 1 / R of the input's frame rate, so whatever brings a
+        # table at the input's rate is refused - frame targets, alignment windows, teacher scores - before anything is built
+        if time_reduce_config(nnet_config)[0]:
+            tabled = [name for name, on in (("objective = %s" % objective, objective != "ctc"),
+                                            ("align_window", align_window is not None),
+                                            ("teacher_weight", teacher_weight is not None)) if on]
+            if tabled:
+                raise ValueError("time_reduce_layers does not combine with %s: its table is at the input's frame rate, the "
+                                 "logits are not (re-timed tables are not built)" % ", ".join(tabled))
         self.model = Model(nnet_config, device, seed=seed)
+        self.time_reduce_short = 0       # utterances whose labels (+ adjacent repeats) no longer fit the output frames
         self.training = learn_rate is not None
         self.learn_rate = learn_rate
         self.clip_norm = clip_norm
@@ -421,8 +431,10 @@ class CTCGraph:
             self.sm_weight, self.sm_logq = _label_smoothing_setup(nnet_config, dev)
         self.keys = ["nnet_input", "sequence_length", "logits", "raw_target", "nnet_target", "size", "eval_loss",
                      "loss", "eval", "global_step", "summary"] + (["lrate", "train"] if self.training else [])
+        if self.model.time_factor > 1:
+            self.keys.append("output_length")            # ceil(sequence_length / R): the lengths of the logits
         if self.consistency_weight is not None:
-            self.keys.append("eval_size")                # what ``eval`` is to be divided by: ``size`` counts both views
+            self.keys.append("eval_size")               # what ``eval`` is to be divided by: ``size`` counts both views
 
     # the reference's graph is a dict; give the same key access
     def __contains__(self, key):
@@ -582,6 +594,8 @@ class CTCGraph:
                                fetch_logits=fetch_logits, train=train, flat_host=up.flat, offs_host=up.offs, seq_host=up.seq,
                                frame_target=frame_target, windows=windows, teacher=up.teacher)
         out["sequence_length"] = np.concatenate([up.seq, up.seq]) if "cr_loss" in out else up.seq   # what the device processed
+        if self.model.time_factor > 1:                    # the lengths of the logits, of ``decoded`` and of every loss term
+            out["output_length"] = self.model.output_lengths(out["sequence_length"])
         return out
 
     def step_device(self, x, seq_d, flat_d, offs_d, maxlen, size, fetch_eval=False, fetch_logits=False, train=None,
@@ -642,7 +656,21 @@ class CTCGraph:
                 specaug_counts = augment.masked_shares(augment.mask_plan(self.drop_seed, b.seq, self.spec_augment, sub),
                                                        b.seq, self.spec_augment, sub)
         logits = self.model.forward(x, b.seq_d, drop_seed=self.drop_seed, seq_len_host=b.seq)      # [T,B,V]
+        short = 0
+        if self.model.time_factor > 1:
+            # pyramidal BiLSTM: the logits are [ceil(T / R), B, V].  EVERYTHING that reads them from here on - criterion,
+            # greedy decode, consistency term, the criterion options' sums - gets the OUTPUT lengths, on the device and on the
+            # host: a loss kernel walking input lengths over these logits would read past the buffer
+            out_len = self.model.output_lengths
+            short = self._time_reduce_short(b, out_len)
+            T_out = logits.shape[0]
+            b = SimpleNamespace(**dict(vars(b), seq_d=out_len(b.seq_d).clamp_(max=T_out),
+                                       seq=None if b.seq is None else np.minimum(out_len(b.seq), T_out),
+                                       pairs=None if b.pairs is None else out_len(b.pairs).clamp_(max=T_out)))
+            assert logits.shape[0] == self.model.output_frames(x.shape[0]), (tuple(logits.shape), tuple(x.shape))
         out, status = self._finish_step(logits, b, fetch_eval=fetch_eval, fetch_logits=fetch_logits, train=train)
+        if status == 0:
+            self.time_reduce_short += short
         if status == 0 and train and self.spec_augment is not None:          # a failed step is re-run: count it once
             self.specaug_steps += 1
             if specaug_counts is not None:
@@ -652,7 +680,23 @@ class CTCGraph:
                 self.specaug_bins += specaug_counts[3]
         return out, status
 
-    KD_KEYS = ("kd_loss", "kd_frames", "kd_agree")           # the teacher term's outputs (objective = kd: the criterion's)
+    @staticmethod
+    def _time_reduce_short(b, out_len):
+        """How many utterances of the step no longer fit the logits of a pyramidal model: labels + adjacent repeats (each
+        needs a blank between) > output length.  From the host's labels and lengths (0 when the step has none: step_device
+        without them); under consistency_weight each utterance counts once.  The criteria handle these themselves - loss 0
+        when skipped, +inf without a path."""
+        if b.flat is None or b.offs is None or b.seq is None:
+            return 0
+        flat, offs, frames = np.asarray(b.flat), np.asarray(b.offs), out_len(b.seq)
+        n = len(frames) if b.pairs is None else int(b.pairs.numel())
+        short = 0
+        for u in range(n):
+            lab = flat[offs[u]:offs[u + 1]]
+            short += int(len(lab) + int((lab[1:] == lab[:-1]).sum()) > int(frames[u]))
+        return short
+
+    KD_KEYS = ("kd_loss", "kd_frames", "kd_agree")          # the teacher term's outputs (objective = kd: the criterion's)
     CR_KEYS = ("cr_loss", "cr_frames", "cr_agree")           # the consistency term's
 
     # A criterion calls its ``ops.*`` loss on the logits and returns (grad, scalars, outputs): the gradient buffer that the
@@ -823,6 +867,9 @@ class CTCGraph:
         and ``ops.ctc_loss_star`` on the same logits, no gradient - what a per-utterance transcript report is written from;
         ``ali``, ``label_index`` and ``score`` are what they are without it."""
         star = CRITERION_OPTIONS["star_penalty"]
+        if self.model.time_factor > 1:
+            raise ValueError("time_reduce_layers does not combine with alignment: an alignment names a symbol per input frame, "
+                             "the logits come once per %d of them" % self.model.time_factor)
         if star_penalty is not None:
             star_penalty = star.check(star_penalty)
         x, seq_d, seq, flat_d, offs_d, flat, offs, maxlen = self._upload(batch)
@@ -910,7 +957,9 @@ class InferenceGraph:
             out = self.model.forward(xd, sd)
             return out, int(ops.lstm_status(dev).item())
 
-        return self._fallback.run(run, error="LSTM recurrence failed on the launch train as well"), seq
+        # (pyramidal BiLSTM: the logits are [ceil(T / R), B, V] and the second value their lengths, ceil(T_i / R))
+        return (self._fallback.run(run, error="LSTM recurrence failed on the launch train as well"),
+                self.model.output_lengths(seq))
 
     def restore(self, path):
         load_params(self.model.ps, path)
@@ -1001,6 +1050,9 @@ def create_graph_for_training_kd(pipeline, nnet_config, learn_rate, clip_norm=5.
 
 def create_graph_for_alignment(pipeline, nnet_config, device="cuda"):
     """A CTCGraph that is only asked to ``align`` (new, no reference counterpart): no optimizer, no dropout."""
+    if time_reduce_config(nnet_config)[0]:
+        raise ValueError("time_reduce_layers does not combine with alignment: an alignment names a symbol per input frame, "
+                         "the logits come once per R of them")
     return CTCGraph(pipeline, dict(nnet_config, is_training=False), device=device)
 
 

@@ -67,10 +67,13 @@ class ParamStore:
         self.peep = False if self.cudnn else (True if not self.blstm else bool(cfg.get("use_peepholes") or False))
         self.num_layers = cfg["num_layers"]
         self.E = (cfg.get("num_experts") or 0) if self.blstm else 0
+        # pyramidal BiLSTM (extension keys time_reduce_layers / time_reduce_factor): a reduced layer reads r
+        # frames of the layer below side by side - its kernels are r times as tall in their input part, nothing else moves
+        self.time_reduce, self.time_reduce_factor = time_reduce_config(cfg)
         specs = []       # (name, shape, kind)
         for i in range(self.num_layers):
             if self.blstm:
-                I = D if i == 0 else 2 * self.Pout
+                I = D if i == 0 else (self.time_reduce_factor if i in self.time_reduce else 1) * 2 * self.Pout
                 prefixes = ["fd%d/frnn%d" % (i, i), "bd%d/brnn%d" % (i, i)]       # bilstm.py:135,156,178,187
             elif self.cudnn:
                 I = D if i == 0 else N
@@ -179,7 +182,11 @@ class ParamStore:
         for name in self.names():
             a = np.asarray(params[name], np.float32)
             if tuple(a.shape) != tuple(self.shapes[name]):
-                raise ValueError("shape mismatch for %s: %s vs %s" % (name, a.shape, self.shapes[name]))
+                why = ""
+                if self.time_reduce and self.kinds[name] == "lstm_kernel":
+                    why = (" (time_reduce_layers = %s widens the input of those layers %d times: a plain model's checkpoint "
+                           "does not fit)" % (",".join(str(l) for l in self.time_reduce), self.time_reduce_factor))
+                raise ValueError("shape mismatch for %s: %s vs %s%s" % (name, a.shape, self.shapes[name], why))
             self.p(name).copy_(torch.from_numpy(np.ascontiguousarray(self._to_internal(name, a))))
         for name, shape, _ in self.aux_specs:        # moving averages: restored when the checkpoint has them
             if name in params:
@@ -243,6 +250,7 @@ def x3_forward_recurrence(N):
 
 
 _PACK_FALLBACK_LOGGED = False      # "pack_frames needs fp32" is said once per process
+_PACK_REDUCE_LOGGED = False        # ... and so is "pack_frames runs padded with time_reduce_layers"
 
 X3_FORCE = False          # tests: every eligible product on the bf16x3 kernels, whatever its size
 X3_MIN_FILL = int(os.environ.get("LC_X3_MIN_FILL", "45"))     # per cent of whole 256-CU rounds (development knob)
@@ -320,6 +328,65 @@ def row_conv_config(cfg):
     return int(v)
 
 
+TIME_REDUCE_FACTORS = (2, 4)      # the library's range of r (lc_time_reduce_fwd)
+
+
+def time_reduce_config(cfg):
+    """(layers, r) of the pyramidal-BiLSTM keys ``time_reduce_layers`` / ``time_reduce_factor`` (extension),
+    validated: ``layers`` the ascending tuple of 0-based indices of the layers whose INPUT joins r consecutive frames of the
+    layer below into one frame r times as wide, each in 1 .. num_layers - 1; ((), 2) when the first key is absent or 0 -
+    today's model, and the factor is then not read.  The key comes from ``parse_config`` as an int (one index) or a string (a
+    comma list).  Like the chunk keys it changes what the model computes, so what cannot run it is refused here."""
+    v = cfg.get("time_reduce_layers")
+    if v is None or (isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v == 0):
+        return (), 2
+    bad = ValueError("time_reduce_layers must be 0 (off) or strictly ascending layer indices in 1 .. num_layers - 1 (one "
+                     "integer or a comma list), got %r" % (v,))
+    if isinstance(v, bool):
+        raise bad
+    if isinstance(v, (int, np.integer)):
+        layers = [int(v)]
+    elif isinstance(v, str):
+        try:
+            layers = [int(tok) for tok in v.split(",")]
+        except ValueError:
+            raise bad from None
+    elif isinstance(v, (list, tuple)) and all(isinstance(e, (int, np.integer)) and not isinstance(e, bool) for e in v):
+        layers = [int(e) for e in v]
+    else:
+        raise bad
+    L = int(cfg["num_layers"])
+    if not layers or any(l < 1 or l > L - 1 for l in layers) or any(a >= b for a, b in zip(layers, layers[1:])):
+        raise ValueError("time_reduce_layers must be strictly ascending layer indices in 1 .. num_layers - 1 = %d, got %r"
+                         % (L - 1, v))
+    r = cfg.get("time_reduce_factor")
+    r = 2 if r is None else r
+    lo, hi = TIME_REDUCE_FACTORS
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < lo or r > hi:
+        raise ValueError("time_reduce_factor (read with time_reduce_layers) must be an integer in %d..%d, got %r" % (lo, hi, r))
+    if cfg.get("nnet_type", "blstm") != "blstm":
+        raise ValueError("time_reduce_layers widens a layer's input, which nnet_type = blstm alone allows; the residual and "
+                         "batch-norm rules of nnet_type = %s tie input width to output width" % cfg.get("nnet_type"))
+    cd = str(cfg.get("compute_dtype") or "fp32").lower()
+    if cd not in ("fp32", "float32", "f32"):
+        raise ValueError("time_reduce_layers is built for compute_dtype = fp32 only, got compute_dtype = %s (its shadow-only "
+                         "activations have no fp32 layer output to re-lay)" % cd)
+    if chunk_config(cfg)[0] > 0:
+        raise ValueError("time_reduce_layers does not combine with chunk_frames / lookahead_frames (the chunk layout is built "
+                         "at one frame rate)")
+    return tuple(layers), int(r)
+
+
+def time_reduce_info_line(cfg):
+    """The INFO line of nnet-init / -train / -validate / -forward when the key is on, else None."""
+    layers, r = time_reduce_config(cfg)
+    if not layers:
+        return None
+    R = r ** len(layers)
+    return ("pyramidal BiLSTM: time_reduce_layers = %s, time_reduce_factor = %d: R = %d, the logits come once per %d model "
+            "frames (%d raw frames)" % (",".join(str(l) for l in layers), r, R, R, R * max(int(cfg.get("subsample") or 0), 1)))
+
+
 def row_conv_identity(shape):
     """The filter that leaves the model as it was: row 0 ones, the lookahead rows zeros."""
     w = np.zeros(shape, np.float32)
@@ -388,6 +455,12 @@ class Model:
         # lookahead - one depthwise filter over the next tau frames of the top layer's output (after its batch norm), in front
         # of the head (lc_row_conv_fwd / lc_row_conv_bwd).  Always fp32; one more parameter, row_conv/kernel.
         self.row_conv = row_conv_config(self.cfg)
+        # Extension keys time_reduce_layers = l[,m,...], time_reduce_factor = r (absent or 0: off, the plain model to the bit):
+        # the pyramidal BiLSTM - the input of each listed layer is r consecutive frames of the layer below side by side
+        # (lc_time_reduce_fwd / lc_time_reduce_bwd), and everything from that layer up runs on ceil(T / r)
+        # frames with lengths ceil(len / r).  The listed layers' kernels are wider: a plain checkpoint does not fit.
+        self.time_reduce, self.time_reduce_factor = time_reduce_config(self.cfg)
+        self.time_factor = self.time_reduce_factor ** len(self.time_reduce)      # R: input frames per logit frame, 1 when off
         self.device = torch.device(device)
         self.ps = ParamStore(self.cfg, self.device)
         self.ps.init_random(seed)
@@ -457,7 +530,15 @@ class Model:
                 from . import tflog
                 tflog.info("pack_frames is built for compute_dtype = fp32 only; compute_dtype = %s runs on the padded rows" % cd)
             self.pack_frames = False
-        self.packed = False          # what the last forward() did: True = the input products ran on packed frames
+        if self.pack_frames and self.time_reduce:
+            # (the frame map is built at one frame rate)
+            global _PACK_REDUCE_LOGGED
+            if not _PACK_REDUCE_LOGGED:
+                _PACK_REDUCE_LOGGED = True
+                from . import tflog
+                tflog.info("pack_frames is built for one frame rate; with time_reduce_layers the model runs on the padded rows")
+            self.pack_frames = False
+        self.packed = False         # what the last forward() did: True = the input products ran on packed frames
         self._frame_map = None       # (key, the lengths the key was made from, FrameMap) of the last ragged batch
 
     def lookahead_horizon(self):
@@ -469,6 +550,21 @@ class Model:
         if not self.chunk:
             return None
         return chunk_horizon(self.ps.num_layers, self.chunk, self.lookahead) - self.chunk
+
+    def output_frames(self, T):
+        """Frames of the logits for T input frames: T with ceil(. / r) applied once per reduced layer (= ceil(T / R))."""
+        T = int(T)
+        for _ in self.time_reduce:
+            T = ops.time_reduce_frames(T, self.time_reduce_factor)
+        return T
+
+    def output_lengths(self, seq_len):
+        """The lengths the logits have for input lengths ``seq_len``: ceil(len / R).  A device tensor is answered on its
+        device with integer ops (no synchronisation), anything else as a numpy int32 array.  ``seq_len`` itself when the
+        model has no reduction."""
+        for _ in self.time_reduce:
+            seq_len = ops.time_reduce_lengths(seq_len, self.time_reduce_factor)
+        return seq_len
 
     def frame_map(self, seq_len, T, B, seq_len_host=None):
         """The FrameMap of this batch, built once per distinct batch.  With ``seq_len_host`` (the lengths as a host array: a
@@ -609,7 +705,8 @@ class Model:
 
     # ------------------------------------------------------------------------------------ forward
     def forward(self, x, seq_len, drop_seed=0, seq_len_host=None):
-        """x [T,B,D] f32 cuda, seq_len [B] int32 cuda -> logits [T,B,V] (time-major).  seq_len_host: the same lengths as a
+        """x [T,B,D] f32 cuda, seq_len [B] int32 cuda -> logits [T,B,V] (time-major; with time_reduce_layers
+        [output_frames(T),B,V], whose lengths are output_lengths(seq_len)).  seq_len_host: the same lengths as a
         host array, if the caller has them (pack_frames then needs no device-to-host copy for a new batch)."""
         ps = self.ps
         self._shadows.clear()                       # parameters moved since the last step; activations are new
@@ -639,7 +736,17 @@ class Model:
         if ps.use_bn:
             inp = batch_norm("drnn_bn_0_0", inp)                                      # lstm.py:271-277
         layers = []
+        # from here on T, rows and seq_len are the CURRENT layer's: a reduced layer changes all three
         for i in range(ps.num_layers):
+            reduced = i in self.time_reduce
+            if reduced:
+                # r frames of the layer below side by side (a fresh fp32 tensor; dead frames and the cut-short last group +0),
+                # and this layer and everything above it on ceil(T / r) frames; the lengths stay on the device
+                r = self.time_reduce_factor
+                inp = ops.time_reduce_fwd(inp, seq_len, T, B, r)
+                seq_len = ops.time_reduce_lengths(seq_len.clamp(0, T), r)
+                T = ops.time_reduce_frames(T, r)
+                rows = T * B
             cells = [self._cell(p) for p in self._prefixes(i)]
             ndir = len(cells)
             Y = torch.empty((rows, ndir * P), dtype=torch.float32, device=dev)
@@ -730,7 +837,8 @@ class Model:
                         ops.length_mask_(Y, seq_len, T, B)    # dynamic_rnn zeroes the wrapped cell's output there
                 if self.keep < 1.0:
                     ops.dropout_scale(Y, self.keep, drop_seed, 2 * i)
-            layers.append(dict(inp=inp, inp_packed=inp_packed, dirs=dirs, cells=cells, Y=Y, residual=residual))
+            layers.append(dict(inp=inp, inp_packed=inp_packed, dirs=dirs, cells=cells, Y=Y, residual=residual, T=T,
+                               seq_len=seq_len, reduced=reduced))
             inp = batch_norm("drnn_bn%d" % i, Y) if ps.use_bn else Y                  # lstm.py:288-294
         pre_conv = None
         if self.row_conv:
@@ -746,6 +854,7 @@ class Model:
             head = dict(q=q, pi=pi)
         else:
             logits = self._mm(inp, ps.p("Variable"), bias=ps.p("Variable_1"))
+        # (T and seq_len: the top layer's - what the head, the logits and encoder() are at; each layer keeps its own)
         self.saved = dict(layers=layers, head=head, T=T, B=B, seq_len=seq_len, drop_seed=drop_seed, bn=bn_saved,
                           top=inp, pre_conv=pre_conv, frames=(pk_rows, pk_inverse) if self.packed else None,
                           chunks=(Tc, Bc, len_c) if chunked else None)
@@ -805,12 +914,14 @@ class Model:
                                    ps.g(name + "/gamma"), ps.g(name + "/beta"), dx=d)
 
 
-        def masked_dY(i, width):
+        def masked_dY(i, width, across_reduction=False):
             """The epilogue that finishes layer i's dY inside the product writing it (the DropoutWrapper's backward: the
             forward mask again, per direction), plus the bf16 shadow both products of each half (dh, dproj) read -
             or (None, None) when layer i masks in a pass of its own."""
-            if not (self.fuse_dropout and ps.blstm and self.keep < 1.0 and not ps.use_bn) or packed:
-                return None, None          # (packed: the mask hashes the PADDED row index - it goes on the unpacked dY below)
+            if not (self.fuse_dropout and ps.blstm and self.keep < 1.0 and not ps.use_bn) or packed or across_reduction:
+                # (packed: the mask hashes the PADDED row index - it goes on the unpacked dY below; across a time reduction:
+                # it hashes the index at layer i's own frame rate - it goes on the un-reduced dY)
+                return None, None
             d16 = (torch.empty((rows, width), dtype=torch.bfloat16, device=dl.device)
                    if self.bf16 and self.use_shadows and P % 4 == 0 else None)
             # (shadow_only: dY is read through the shadow by both products of each half - dh = half . proj^T, dproj = hs^T half)
@@ -839,6 +950,9 @@ class Model:
         for i in reversed(range(ps.num_layers)):
             L = sv["layers"][i]
             cells, dirs, inp = L["cells"], L["dirs"], L["inp"]
+            # this layer's own frame count, rows and lengths (all layers alike without time_reduce_layers)
+            T, seq_len = L["T"], L["seq_len"]
+            rows = T * B
             ndir = len(cells)
             need_dinp = i > 0 or ps.use_bn
             dres = None
@@ -917,7 +1031,7 @@ class Model:
                 bdirs[1]["gates"] = ops.chunk_fold(bdirs[1]["gates_c"], T, B, self.chunk, self.lookahead, sum_copies=True,
                                                    seq_len=sv["seq_len"])
             else:
-                ops.lstm_bwd(bdirs, sv["seq_len"], T, B, N, bf16=self.bf16, x3=self.x3_rec_bwd)
+                ops.lstm_bwd(bdirs, seq_len, T, B, N, bf16=self.bf16, x3=self.x3_rec_bwd)
             if buckets is not None and i + 1 < ps.num_layers and not self.overlap_wgrad:
                 buckets.issue(*self.layer_grad_range(i + 1))      # runs beside this layer's weight-gradient GEMMs
             for bd in bdirs:
@@ -936,7 +1050,8 @@ class Model:
                 dinp = torch.empty((rows, inp.shape[1]), dtype=torch.float32, device=dY.device)
             # the buffer the dX products write: dinp itself, or its packed form
             dxo = torch.empty((pk_rows.shape[0], inp.shape[1]), dtype=torch.float32, device=dY.device) if need_dinp and packed else dinp
-            ep, next16 = masked_dY(i - 1, inp.shape[1]) if i > 0 else (None, None)    # rides on the LAST product into dinp
+            # rides on the LAST product into dinp
+            ep, next16 = masked_dY(i - 1, inp.shape[1], across_reduction=L["reduced"]) if i > 0 else (None, None)
             overlap = self.overlap_wgrad and i > 0
             side_x3 = not (overlap and self.x3_side_f32)
             # bf16 shadows, both directions: dinp = dz_f . Kx_f^T + dz_b . Kx_b^T as ONE product whose reduction walks both
@@ -1034,6 +1149,11 @@ class Model:
             if need_dinp:
                 if dres is not None:
                     ops.dropout_scale(dres, 1.0, 0, 0, out=dinp, accumulate=True)
+                if L["reduced"]:
+                    # dinp is [rows, r * 2P] at this layer's rate: each frame's r parts go back to the frames of the layer
+                    # below they came from (its dead frames +0); that layer masks its dY in a pass of its own, at its own rate
+                    below = sv["layers"][i - 1]
+                    dinp = ops.time_reduce_bwd(dinp, below["seq_len"], below["T"], B, self.time_reduce_factor)
                 dY, dY16, premasked = dinp, next16, ep is not None
         if ps.use_bn:
             batch_norm_bwd("drnn_bn_0_0", dY)

@@ -946,6 +946,76 @@ def row_conv_bwd(x2d, dy2d, w, seq_len, T, B, want_dx=True, want_dw=True, dx=Non
     return dx, dw
 
 
+# ------------------------------------------------------------------------------------------ time reduction (pyramidal BiLSTM)
+TIME_REDUCE_MIN_FACTOR, TIME_REDUCE_MAX_FACTOR = 2, 4       # the library's range of r (include/lstm_ctc_hip.h)
+
+
+def time_reduce_frames(T, r):
+    """ceil(T / r): the frames (or, for a length, the live frames) left after joining r consecutive ones."""
+    return -(-int(T) // int(r))
+
+
+def time_reduce_lengths(seq_len, r):
+    """ceil(seq_len / r), elementwise: the lengths behind a reduction by r.  A device tensor stays on its device (integer
+    ops, no kernel of ours and no synchronisation) and comes back int32 and contiguous; anything else comes back as a numpy
+    int32 array."""
+    r = int(r)
+    if r < 1:
+        raise ValueError("time_reduce_lengths: need r >= 1, got %r" % (r,))
+    if isinstance(seq_len, torch.Tensor):
+        return torch.div(seq_len.to(torch.int32) + (r - 1), r, rounding_mode="floor").to(torch.int32).contiguous()
+    a = np.asarray(seq_len)
+    return ((a.astype(np.int64) + (r - 1)) // r).astype(np.int32)
+
+
+def _time_reduce_args(seq_len, T, B, C, r, narrow, wide):
+    if not (TIME_REDUCE_MIN_FACTOR <= int(r) <= TIME_REDUCE_MAX_FACTOR):
+        raise ValueError("time reduction: r must be in %d..%d, got %r" % (TIME_REDUCE_MIN_FACTOR, TIME_REDUCE_MAX_FACTOR, r))
+    To = time_reduce_frames(T, r)
+    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+    for m, shape in ((narrow, (T * B, C)), (wide, (To * B, r * C))):
+        assert m.dim() == 2 and m.dtype == torch.float32 and m.stride(1) == 1 and tuple(m.shape) == shape, \
+            (tuple(m.shape), m.stride(), shape)
+    return To
+
+
+def time_reduce_fwd(x2d, seq_len, T, B, r, out=None):
+    """Time reduction (lc_time_reduce_fwd): x2d [T*B, C] time-major f32 (a 2-D view, last stride 1), seq_len [B] int32 -> out
+    [ceil(T / r) * B, r * C], out[to, b, j * C + c] = x[r * to + j, b, c] where frame r * to + j of utterance b is live, +0
+    elsewhere.  Every element of out is written; dead frames of x are never read."""
+    lib = _lib.load()
+    _require_cuda(x2d, seq_len, out)
+    T, B, r = int(T), int(B), int(r)
+    assert x2d.dim() == 2
+    C = x2d.shape[1]
+    if out is None:
+        out = torch.empty((time_reduce_frames(T, r) * B, r * C), dtype=torch.float32, device=x2d.device)
+    _time_reduce_args(seq_len, T, B, C, r, x2d, out)
+    ev = _prof_begin()
+    _lib.check(lib.lc_time_reduce_fwd(_ptr(x2d), _rows_pitch(x2d, C), T, B, C, r, _ptr(seq_len), _ptr(out),
+                                      _rows_pitch(out, r * C), _stream()), "lc_time_reduce_fwd")
+    _prof_end("time_reduce", 8.0 * T * B * C, ev)
+    return out
+
+
+def time_reduce_bwd(dy2d, seq_len, T, B, r, out=None):
+    """The adjoint of time_reduce_fwd (lc_time_reduce_bwd): dy2d [ceil(T / r) * B, r * C] -> out [T*B, C], out[t, b, c] =
+    dy[t // r, b, (t % r) * C + c] in live frames, +0 in dead ones.  Every element of out is written."""
+    lib = _lib.load()
+    _require_cuda(dy2d, seq_len, out)
+    T, B, r = int(T), int(B), int(r)
+    assert dy2d.dim() == 2 and r >= 1 and dy2d.shape[1] % r == 0, (tuple(dy2d.shape), r)
+    C = dy2d.shape[1] // r
+    if out is None:
+        out = torch.empty((T * B, C), dtype=torch.float32, device=dy2d.device)
+    _time_reduce_args(seq_len, T, B, C, r, out, dy2d)
+    ev = _prof_begin()
+    _lib.check(lib.lc_time_reduce_bwd(_ptr(dy2d), _rows_pitch(dy2d, r * C), T, B, C, r, _ptr(seq_len), _ptr(out),
+                                      _rows_pitch(out, C), _stream()), "lc_time_reduce_bwd")
+    _prof_end("time_reduce", 8.0 * T * B * C, ev)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ SpecAugment
 def _tbd_pitch(t, T, B, D):
     """Row pitch of a time-major [T, B, D] tensor whose T * B rows lie at one pitch (a column window of a wider buffer is
