@@ -368,6 +368,19 @@ def report_row_conv(nnet_config):
         tflog.info(line)
 
 
+def report_layer_norm(nnet_config):
+    """One INFO line when <nnet-config> sets layer_norm (layer normalisation of every layer's output): which
+    layers are normalised, and eps.  A config the model refuses: the FATAL line and exit 1, before a model is built."""
+    from lstm_ctc_amd.nnet.model import layer_norm_info_line
+    try:
+        line = layer_norm_info_line(nnet_config)
+    except ValueError as exc:
+        _fatal(str(exc))
+    if line:
+        from lstm_ctc_amd.nnet import tflog
+        tflog.info(line)
+
+
 def report_time_reduce(nnet_config, args=None, aligning=False):
     """One INFO line when <nnet-config> sets time_reduce_layers (the pyramidal BiLSTM): the layers, r, R and how
     many model and raw frames one frame of the logits stands for.  A config the model refuses, or (``args``) a command line

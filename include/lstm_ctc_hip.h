@@ -708,6 +708,43 @@ int lc_time_reduce_fwd(const float *x, int ldx, int T, int B, int C, int r, cons
 int lc_time_reduce_bwd(const float *dy, int lddy, int T, int B, int C, int r, const int *seq_len, float *dx, int lddx,
                        lc_stream_t stream);
 
+/* ------------------------------------------------------------------ layer normalisation ----- */
+/* Layer normalisation of a layer's output (Ba et al. 2016; no reference counterpart), with the DropoutWrapper
+ * mask behind it.  x, y, dy, dx are time-major [T * B, C] with row pitches ldx / ldy / lddy / lddx in floats (column windows of
+ * wider buffers are fine); gamma, beta, dgamma, dbeta are dense [C]; seq_len is a device [B] int32 and is REQUIRED.  With
+ * len_b = clamp(seq_len[b], 0, T), live(t, b) = t < len_b, m = mean_c x, v = mean_c (x - m)^2 (biased), rstd = 1 / sqrt(v + eps),
+ * xh = (x - m) * rstd, row r = t * B + b, and mask[r, c] = the DropoutWrapper factor (1 / keep or 0) of stream
+ * stream0 + c / drop_width at index r * drop_width + c % drop_width - what lc_dropout_scale gives on the [T * B, drop_width]
+ * column window c / drop_width with stream_id = stream0 + c / drop_width -, 1 when keep == 1:
+ *   lc_layer_norm_fwd   y[r, c]   = mask[r, c] * (gamma[c] * xh[r, c] + beta[c])                        if live, else +0
+ *   lc_layer_norm_bwd   with g = mask * dy, a = gamma * g:
+ *                       dx[r, c]  = rstd * (a[r, c] - mean_c a - xh[r, c] * mean_c (a * xh))            if live, else +0
+ *                       dgamma[c] = sum over live rows of g * xh,   dbeta[c] = sum over live rows of g  (overwritten)
+ *   - One streaming pass each: a row is read once into registers and written once; the backward recomputes m and rstd from x,
+ *     so no statistics are kept between the passes.  The variance is the centred two-pass form, not E[x^2] - m^2.
+ *   - Dead rows are never read (NaN included) and written +0; every element of y, dx, dgamma and dbeta is written on every
+ *     successful call, and nothing outside the windows is touched.
+ *   - With keep < 1, y equals lc_dropout_scale applied to the keep == 1 result, bit for bit.
+ *   - Determinism: no atomics.  Each workgroup of the backward walks a fixed, contiguous share of the rows and leaves one
+ *     [2, C] partial in the workspace; a second kernel adds the partials in a fixed order.  The same call gives the same bits.
+ *   - Pointers: dx may be NULL; dgamma and dbeta are both NULL or both not; not all three.  The workspace is needed for the
+ *     parameter gradients only.  dx == dy with lddx == lddy is allowed (in place); any other overlap of y with x, of dx with x
+ *     or of dx with dy is refused.
+ *   - Elements are indexed in 64 bits.  16-byte accesses when C and the pitches are multiples of 4 and the bases (gamma and beta
+ *     included) 16-byte aligned, a scalar path otherwise.
+ * LC_EINVAL, with nothing launched and no output touched: T, B, C <= 0 or C > 8192 (a design cap: a row lives in one wave's
+ * registers); a NULL required pointer; one of dgamma / dbeta alone; a pitch below C; eps <= 0; keep outside (0, 1]; drop_width
+ * < 1 or not a divisor of C; the overlaps above; a non-NULL dgamma with a workspace below lc_layer_norm_workspace_bytes (0 for
+ * a bad shape). */
+size_t lc_layer_norm_workspace_bytes(int T, int B, int C);
+int lc_layer_norm_fwd(const float *x, int ldx, const float *gamma, const float *beta, int T, int B, int C, float eps,
+                      const int *seq_len, float keep, uint32_t seed, uint32_t stream0, int drop_width,
+                      float *y, int ldy, lc_stream_t stream);
+int lc_layer_norm_bwd(const float *x, int ldx, const float *dy, int lddy, const float *gamma, int T, int B, int C, float eps,
+                      const int *seq_len, float keep, uint32_t seed, uint32_t stream0, int drop_width,
+                      float *dx /* or NULL */, int lddx, float *dgamma, float *dbeta /* both or neither; overwritten */,
+                      void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* ------------------------------------------------------------------ SpecAugment ------------- */
 /* Time and frequency masking of the filterbank input (Park et al., 2019; no reference counterpart), on the spliced and
  * subsampled batch the loader uploads.  x and out are time-major [T * B, D] with row pitches ldx / ldo (floats); out == x (in

@@ -17,7 +17,8 @@ MI355X-first design choices:
 * every LSTM ``kernel``/``bias`` lives permanently in the gate-interleaved column layout the step
   kernel wants; TF's ``[i|j|f|o]`` layout only exists at checkpoint I/O (:meth:`ParamStore.export_tf`);
 * all parameters (and gradients, and optimizer slots) are single flat fp32 buffers: L2-decayed
-  tensors first, the LSTM ``bias`` vectors (the only names containing "bias", nnet/graph.py:185) last.
+  tensors first, the LSTM ``bias`` vectors (the only names containing "bias", nnet/graph.py:185) last - and behind them, with
+  ``layer_norm``, the gains and offsets ``ln{i}/gamma``, ``ln{i}/beta``, undecayed by kind.
 """
 import math
 import os
@@ -105,13 +106,21 @@ class ParamStore:
         self.row_conv = row_conv_config(cfg)
         if self.row_conv:
             specs.append(("row_conv/kernel", (self.row_conv + 1, H), "row_conv"))
+        # layer normalisation (extension key layer_norm): a gain and an offset per layer output.  Kept out of the
+        # L2 decay by kind (a gain decayed towards zero is not wanted), so they lie with the biases behind every decayed tensor
+        # and layer_grad_range and the data-parallel buckets keep their ranges
+        self.layer_norm = layer_norm_config(cfg)
+        if self.layer_norm:
+            for i in range(self.num_layers):
+                specs += [("ln%d/gamma" % i, (H,), "ln_gamma"), ("ln%d/beta" % i, (H,), "ln_beta")]
         if self.E > 0:                                                            # moe.py:33-58
             specs += [("Variable", (H, self.E), "head_w"), ("Variable_1", (self.E,), "head_b"),
                       ("Variable_2", (H, self.E * V), "head_w"), ("Variable_3", (self.E * V,), "head_b")]
         else:                                                                     # bilstm.py:238-248
             specs += [("Variable", (H, V), "head_w"), ("Variable_1", (V,), "head_b")]
-        decayed = [s for s in specs if "bias" not in s[0]]                        # graph.py:183-187
-        plain = [s for s in specs if "bias" in s[0]]
+        undecayed = lambda s: "bias" in s[0] or s[2] in ("ln_gamma", "ln_beta")
+        decayed = [s for s in specs if not undecayed(s)]                          # graph.py:183-187
+        plain = [s for s in specs if undecayed(s)]
         self.specs = decayed + plain
         self.kinds = {s[0]: s[2] for s in self.specs}
         self.shapes = {s[0]: s[1] for s in self.specs}
@@ -169,6 +178,13 @@ class ParamStore:
     def load_tf(self, params):
         """params: dict name -> numpy array in TF layout (tf.trainable_variables shapes)."""
         missing = [n for n in self.names() if n not in params]
+        if self.layer_norm and any(self.kinds[n] == "ln_gamma" for n in missing):
+            raise KeyError("checkpoint has no %s: a model with layer_norm = true cannot start from a plain model's checkpoint "
+                           "(no setting of ln*/gamma and ln*/beta computes what that model computed)"
+                           % ", ".join(n for n in missing if self.kinds[n] == "ln_gamma"))
+        if not self.layer_norm and "ln0/gamma" in params:
+            raise KeyError("checkpoint has ln0/gamma: it was written by a model with layer_norm = true, and this model (no "
+                           "layer_norm key) would compute something else with its other variables")
         if missing == ["row_conv/kernel"]:
             # a plain model's checkpoint: the identity filter computes what that model computed (fine-tuning with lookahead)
             from . import tflog
@@ -229,8 +245,8 @@ class ParamStore:
                     a[bad] = rng.normal(0.0, std, size=int(bad.sum()))
                     bad = np.abs(a) > 2 * std
                 params[name] = a.astype(np.float32)
-            elif kind == "bn_gamma":
-                params[name] = np.ones(shape, np.float32)
+            elif kind in ("bn_gamma", "ln_gamma"):
+                params[name] = np.ones(shape, np.float32)                 # (ln: nothing drawn, like row_conv below)
             elif kind == "row_conv":
                 params[name] = row_conv_identity(shape)            # nothing drawn: the other tensors are the plain model's
             else:
@@ -326,6 +342,31 @@ def row_conv_config(cfg):
         raise ValueError("row_conv_frames gives a unidirectional model (nnet_type = lstm or cudnnlstm) lookahead; nnet_type = "
                          "blstm already reads the whole future")
     return int(v)
+
+
+def layer_norm_config(cfg):
+    """Whether the key ``layer_norm`` (extension) is on, validated: False when it is absent or false - today's
+    model -, True for true; anything that is not a boolean is refused, and so is the key together with ``use_bn`` (two
+    normalisations of the same tensor).  Like the chunk keys it changes what the model computes."""
+    v = cfg.get("layer_norm")
+    if v is None:
+        return False
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("layer_norm must be true or false, got %r" % (v,))
+    if not v:
+        return False
+    if cfg.get("use_bn"):
+        raise ValueError("layer_norm does not combine with use_bn: both would normalise every layer's output")
+    return True
+
+
+def layer_norm_info_line(cfg):
+    """The INFO line of nnet-init / -train / -validate / -forward / -align when the key is on, else None."""
+    if not layer_norm_config(cfg):
+        return None
+    L = int(cfg["num_layers"])
+    return ("layer normalisation: layer_norm = true: the outputs of layers 0..%d are normalised over their columns (both "
+            "directions of a blstm layer together), dropout behind it; eps = %g" % (L - 1, ops.LN_EPS))
 
 
 TIME_REDUCE_FACTORS = (2, 4)      # the library's range of r (lc_time_reduce_fwd)
@@ -461,6 +502,10 @@ class Model:
         # frames with lengths ceil(len / r).  The listed layers' kernels are wider: a plain checkpoint does not fit.
         self.time_reduce, self.time_reduce_factor = time_reduce_config(self.cfg)
         self.time_factor = self.time_reduce_factor ** len(self.time_reduce)      # R: input frames per logit frame, 1 when off
+        # Extension key layer_norm = true (absent or false: off, the plain model to the bit): every layer's output is normalised
+        # over its columns, with a gain and an offset ln{i}/gamma, ln{i}/beta, and the DropoutWrapper mask moves behind the
+        # normalisation (lc_layer_norm_fwd / lc_layer_norm_bwd).  A plain checkpoint is refused by name.
+        self.layer_norm = layer_norm_config(self.cfg)
         self.device = torch.device(device)
         self.ps = ParamStore(self.cfg, self.device)
         self.ps.init_random(seed)
@@ -627,7 +672,7 @@ class Model:
         dX - see _mm and backward): layer widths in whole 256-tiles, and for a narrow input (layer 0) the padded K-major route,
         which needs rows >= 4096.  The library honours the request in its full-width kernel (N = 1024) and ignores it elsewhere."""
         ps = self.ps
-        return bool(self.shadow_only and self.bf16 and self.use_shadows and ps.blstm and not ps.use_bn and ps.P
+        return bool(self.shadow_only and self.bf16 and self.use_shadows and ps.blstm and not ps.use_bn and not ps.layer_norm and ps.P
                     and ps.N % 256 == 0 and ps.Pout % 256 == 0 and rows % 256 == 0 and rows >= 4096
                     and (I % 256 == 0 or I < 256))
 
@@ -792,12 +837,14 @@ class Model:
                 if dd.get("hs_bf16") is not None:
                     self._adopt_shadow(dd["hs"], dd["hs_bf16"])
             residual = (i == 0 and D == 2 * P) if ps.blstm else False               # bilstm.py:199
-            drop = ps.blstm and self.keep < 1.0                                      # DropoutWrapper on each direction
+            # DropoutWrapper on each direction (layer_norm: Y stays unmasked, the mask goes on the normalised output below)
+            drop = ps.blstm and self.keep < 1.0 and not ps.layer_norm
             # bf16 path: the pass that applies the mask also writes the bf16 shadow the next product reads
             # (round 6: without dropout too - inference, parity runs - when every direction has a projection product to carry it)
             Y16 = (torch.empty((rows, ndir * P), dtype=torch.bfloat16, device=dev)
                    if (drop or (ps.blstm and all(c_["proj"] is not None for c_ in cells)))
-                   and self.bf16 and self.use_shadows and not residual and not ps.use_bn and P % 4 == 0 else None)
+                   and self.bf16 and self.use_shadows and not residual and not ps.use_bn and not ps.layer_norm and P % 4 == 0
+                   else None)
             for d, c in enumerate(cells):
                 half = Y[:, d * P:(d + 1) * P]
                 if c["proj"] is not None:
@@ -835,11 +882,16 @@ class Model:
                     ops.dropout_scale(inp, 1.0, 0, 0, out=Y, accumulate=True)        # ResidualWrapper
                     if ps.use_bn:         # a batch-normalised input is non-zero in the padded frames, but
                         ops.length_mask_(Y, seq_len, T, B)    # dynamic_rnn zeroes the wrapped cell's output there
-                if self.keep < 1.0:
+                if self.keep < 1.0 and not ps.layer_norm:
                     ops.dropout_scale(Y, self.keep, drop_seed, 2 * i)
             layers.append(dict(inp=inp, inp_packed=inp_packed, dirs=dirs, cells=cells, Y=Y, residual=residual, T=T,
                                seq_len=seq_len, reduced=reduced))
             inp = batch_norm("drnn_bn%d" % i, Y) if ps.use_bn else Y                  # lstm.py:288-294
+            if ps.layer_norm:
+                # the next layer (and the top of the stack) reads dropout(LN(Y)): one pass, a fresh fp32 tensor in every
+                # compute_dtype (the bf16 modes cast their own shadow of it); dead frames +0, like the plain model's Y
+                inp = ops.layer_norm_fwd(Y, ps.p("ln%d/gamma" % i), ps.p("ln%d/beta" % i), seq_len, T, B, self.keep, drop_seed,
+                                         2 * i, P if ps.blstm else ndir * P)
         pre_conv = None
         if self.row_conv:
             # lookahead: the head reads sum_j w[j] * top[t + j] over the live frames (fp32 in every compute_dtype; a fresh
@@ -918,7 +970,8 @@ class Model:
             """The epilogue that finishes layer i's dY inside the product writing it (the DropoutWrapper's backward: the
             forward mask again, per direction), plus the bf16 shadow both products of each half (dh, dproj) read -
             or (None, None) when layer i masks in a pass of its own."""
-            if not (self.fuse_dropout and ps.blstm and self.keep < 1.0 and not ps.use_bn) or packed or across_reduction:
+            if (not (self.fuse_dropout and ps.blstm and self.keep < 1.0 and not ps.use_bn and not ps.layer_norm) or packed
+                    or across_reduction):
                 # (packed: the mask hashes the PADDED row index - it goes on the unpacked dY below; across a time reduction:
                 # it hashes the index at layer i's own frame rate - it goes on the un-reduced dY)
                 return None, None
@@ -958,12 +1011,17 @@ class Model:
             dres = None
             if ps.use_bn:
                 dY = batch_norm_bwd("drnn_bn%d" % i, dY)
+            if ps.layer_norm:
+                # dY becomes the gradient of the unmasked Y, in place (the pass applies the forward's mask to dY on load)
+                ops.layer_norm_bwd(L["Y"], dY, ps.p("ln%d/gamma" % i), seq_len, T, B, self.keep, seed, 2 * i,
+                                   P if ps.blstm else ndir * P, dx=dY, dgamma=ps.g("ln%d/gamma" % i),
+                                   dbeta=ps.g("ln%d/beta" % i))
             if ps.blstm:
                 if premasked:                    # the product that wrote dY masked it and wrote its shadow
                     if dY16 is not None:
                         for d in range(ndir):
                             self._adopt_shadow(dY[:, d * P:(d + 1) * P], dY16[:, d * P:(d + 1) * P])
-                elif self.keep < 1.0:
+                elif self.keep < 1.0 and not ps.layer_norm:
                     dY16 = (torch.empty((rows, ndir * P), dtype=torch.bfloat16, device=dY.device)
                             if self.bf16 and self.use_shadows and P % 4 == 0 and dY.stride(0) % 4 == 0 else None)
                     for d in range(ndir):
@@ -974,7 +1032,7 @@ class Model:
                             ops.dropout_scale(half, self.keep, seed, 2 * i + d, shadow=dY16[:, d * P:(d + 1) * P])
                             self._adopt_shadow(half, dY16[:, d * P:(d + 1) * P])
             else:
-                if self.keep < 1.0:
+                if self.keep < 1.0 and not ps.layer_norm:
                     ops.dropout_scale(dY, self.keep, seed, 2 * i)
                 if L["residual"]:
                     if ps.use_bn:

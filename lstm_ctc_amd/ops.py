@@ -1016,6 +1016,92 @@ def time_reduce_bwd(dy2d, seq_len, T, B, r, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ layer normalisation
+LN_EPS = 1e-5               # one constant, like BN_EPS
+LAYER_NORM_MAX_C = 8192     # the library's cap: a row lives in one wave's registers (include/lstm_ctc_hip.h)
+# csrc/layer_norm.hip's launch constants (LN_MAX_GROUPS; 256 threads over rows of at least 4 lanes): more rows than their product
+# and every lane choice's launch walks its rows in more than one pass, and the backward leaves more than one partial per column
+LAYER_NORM_MAX_GROUPS, LAYER_NORM_MAX_ROWS_PER_GROUP = 1024, 64
+
+
+def _layer_norm_args(C, seq_len, T, B, keep, drop_width, vecs, *mats):
+    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+    for v in vecs:
+        assert v.dim() == 1 and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == C, (tuple(v.shape), C)
+    for m in mats:
+        assert m.dim() == 2 and m.dtype == torch.float32 and m.stride(1) == 1 and tuple(m.shape) == (T * B, C), \
+            (tuple(m.shape), m.stride(), (T * B, C))
+    if not 1 <= C <= LAYER_NORM_MAX_C:
+        raise ValueError("layer normalisation: C must be in 1..%d, got %d" % (LAYER_NORM_MAX_C, C))
+    if not 0.0 < keep <= 1.0:
+        raise ValueError("layer normalisation: keep must be in (0, 1], got %r" % (keep,))
+    if drop_width < 1 or C % drop_width:
+        raise ValueError("layer normalisation: drop_width %r does not divide C = %d" % (drop_width, C))
+
+
+def layer_norm_fwd(x2d, gamma, beta, seq_len, T, B, keep=1.0, seed=0, stream0=0, drop_width=None, out=None):
+    """Layer normalisation with the dropout mask behind it (lc_layer_norm_fwd): x2d [T*B, C] time-major f32 (a 2-D view, last
+    stride 1), gamma / beta [C], seq_len [B] int32 -> out [T*B, C] = mask * (gamma * (x - m) / sqrt(v + LN_EPS) + beta) in live
+    rows (m, v: mean and biased variance over the C columns), +0 in dead ones.  keep < 1: column c takes the DropoutWrapper
+    factor of stream ``stream0 + c // drop_width`` at index ``row * drop_width + c % drop_width`` (drop_width defaults to C).
+    Every element of out is written; dead rows of x are never read."""
+    lib = _lib.load()
+    _require_cuda(x2d, gamma, beta, seq_len, out)
+    T, B = int(T), int(B)
+    assert x2d.dim() == 2
+    C = x2d.shape[1]
+    drop_width = C if drop_width is None else int(drop_width)
+    if out is None:
+        out = torch.empty((T * B, C), dtype=torch.float32, device=x2d.device)
+    _layer_norm_args(C, seq_len, T, B, keep, drop_width, (gamma, beta), x2d, out)
+    ev = _prof_begin()
+    _lib.check(lib.lc_layer_norm_fwd(_ptr(x2d), _rows_pitch(x2d, C), _ptr(gamma), _ptr(beta), T, B, C, LN_EPS, _ptr(seq_len),
+                                     float(keep), int(seed) & 0xFFFFFFFF, int(stream0), drop_width, _ptr(out),
+                                     _rows_pitch(out, C), _stream()), "lc_layer_norm_fwd")
+    _prof_end("layer_norm", 8.0 * T * B * C, ev)         # HBM bytes: x read, y written
+    return out
+
+
+def layer_norm_bwd(x2d, dy2d, gamma, seq_len, T, B, keep=1.0, seed=0, stream0=0, drop_width=None, want_dx=True,
+                   want_dparams=True, dx=None, dgamma=None, dbeta=None):
+    """Gradients of layer_norm_fwd (lc_layer_norm_bwd) -> (dx [T*B, C] or None, dgamma [C] or None, dbeta [C] or None), from the
+    layer's input x2d alone (mean and variance are recomputed) and the same mask arguments: with g = mask * dy and xh the
+    normalised x, dx = rstd * (gamma g - mean(gamma g) - xh * mean(gamma g xh)) in live rows and +0 in dead ones, dgamma = sum
+    over live rows of g * xh, dbeta = sum over live rows of g, both overwritten.  ``dx``: optional destination, dy2d itself for
+    the in-place form.  The workspace of the parameter gradients is owned here."""
+    lib = _lib.load()
+    _require_cuda(x2d, dy2d, gamma, seq_len, dx, dgamma, dbeta)
+    if not (want_dx or want_dparams):
+        raise ValueError("layer_norm_bwd: want_dx and want_dparams are both false")
+    T, B = int(T), int(B)
+    assert x2d.dim() == 2
+    C = x2d.shape[1]
+    drop_width = C if drop_width is None else int(drop_width)
+    _layer_norm_args(C, seq_len, T, B, keep, drop_width, (gamma,), x2d, dy2d)
+    if want_dx:
+        if dx is None:
+            dx = torch.empty((T * B, C), dtype=torch.float32, device=dy2d.device)
+        _layer_norm_args(C, seq_len, T, B, keep, drop_width, (), dx)
+    else:
+        dx = None
+    ws, nbytes = None, 0
+    if want_dparams:
+        dgamma = torch.empty(C, dtype=torch.float32, device=dy2d.device) if dgamma is None else dgamma
+        dbeta = torch.empty(C, dtype=torch.float32, device=dy2d.device) if dbeta is None else dbeta
+        _layer_norm_args(C, seq_len, T, B, keep, drop_width, (dgamma, dbeta))
+        nbytes = lib.lc_layer_norm_workspace_bytes(T, B, C)
+        ws = workspace("layer_norm", nbytes, dy2d.device)
+    else:
+        dgamma = dbeta = None
+    ev = _prof_begin()
+    _lib.check(lib.lc_layer_norm_bwd(_ptr(x2d), _rows_pitch(x2d, C), _ptr(dy2d), _rows_pitch(dy2d, C), _ptr(gamma), T, B, C,
+                                     LN_EPS, _ptr(seq_len), float(keep), int(seed) & 0xFFFFFFFF, int(stream0), drop_width,
+                                     _ptr(dx), _rows_pitch(dx, C) if dx is not None else C, _ptr(dgamma), _ptr(dbeta), _ptr(ws),
+                                     nbytes, _stream()), "lc_layer_norm_bwd")
+    _prof_end("layer_norm", 12.0 * T * B * C, ev)        # HBM bytes: x and dy read, dx written
+    return dx, dgamma, dbeta
+
+
 # ------------------------------------------------------------------------------------------ SpecAugment
 def _tbd_pitch(t, T, B, D):
     """Row pitch of a time-major [T, B, D] tensor whose T * B rows lie at one pitch (a column window of a wider buffer is
