@@ -1,8 +1,8 @@
 // layer_norm.hip - layer normalisation of a layer's output between the LSTM layers (lc_layer_norm_fwd / lc_layer_norm_bwd,
-// include/lstm_ctc_hip.h), with the DropoutWrapper mask behind it.  One streaming pass each with time_reduce.hip's
+// include/lstm_ctc_hip.h), with the DropoutWrapper mask behind it.  One streaming pass each on row_stream.h's
 // skeleton: a row is read once into registers by LPR lanes of one wave, reduced with cross-lane adds, and written once.  Dead
 // rows are written +0 and never read.  No atomics: the parameter gradients go through per-workgroup partials in the workspace.
-#include "common.h"
+#include "row_stream.h"
 
 namespace {
 
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float *__restrict__ x
         len = len < 0 ? 0 : (len > T ? T : len);
         V *dst = reinterpret_cast<V *>(y + r * ldy);
         if (t >= len) {
-            for (int q = lane; q < CV; q += LPR) dst[q] = V{};
+            zero_row<V, LPR>(dst, CV, lane);
             continue;
         }
         const V *src = reinterpret_cast<const V *>(x + r * ldx);
@@ -139,6 +139,7 @@ __global__ __launch_bounds__(BLOCK) void ln_bwd_kernel(const float *__restrict__
         len = len < 0 ? 0 : (len > T ? T : len);
         V *dst = reinterpret_cast<V *>(dx + r * lddx);
         if (t >= len) {
+            // zero_row written out: called, the wide instantiations of this kernel come out with other registers and spills
             if (dx) for (int q = lane; q < CV; q += LPR) dst[q] = V{};
             continue;
         }
@@ -236,34 +237,12 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const float *__restrict__ 
     }
 }
 
-// lanes per row: the power of two in 4 .. 64 that leaves the fewest lanes idle over the row's passes (the widest such, at most 8
-// passes per lane below 64 lanes) - launch_time_reduce's rule inside one wave
-int ln_lanes(int CV)
-{
-    int lpr = 64;
-    long long idle = -1;
-    for (int l = 64; l >= 4; l /= 2) {
-        const int passes = (CV + l - 1) / l;
-        if (passes > 8 && l < 64) break;
-        const long long w = (long long)passes * l - CV;
-        if (idle < 0 || w < idle) { idle = w; lpr = l; }
-    }
-    return lpr;
-}
-
 // the workgroups of the backward over nrows rows at `rpb` rows per workgroup pass, and the row groups each of them walks
 void ln_bwd_shares(long long nrows, int rpb, long long &per, int &nparts)
 {
     const long long groups = (nrows + rpb - 1) / rpb;
     per = (groups + LN_MAX_GROUPS - 1) / LN_MAX_GROUPS;
     nparts = (int)((groups + per - 1) / per);
-}
-
-bool ln_overlap(const float *a, long long lda, long long rows_a, const float *b, long long ldb, long long rows_b, long long C)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((rows_a - 1) * lda + C) * sizeof(float);
-    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + ((rows_b - 1) * ldb + C) * sizeof(float);
-    return !(a1 <= b0 || b1 <= a0);
 }
 
 size_t ln_workspace_bytes(long long nrows, int C)
@@ -294,32 +273,24 @@ extern "C" int lc_layer_norm_fwd(const float *x, int ldx, const float *gamma, co
     LC_CHECK_ARG(eps > 0.f && keep > 0.f && keep <= 1.f, "%s: need eps > 0 and keep in (0, 1], got %g, %g", who, eps, keep);
     LC_CHECK_ARG(drop_width >= 1 && C % drop_width == 0, "%s: drop_width %d does not divide C %d", who, drop_width, C);
     const long long nrows = (long long)T * B;
-    LC_CHECK_ARG(!ln_overlap(x, ldx, nrows, y, ldy, nrows, C), "%s: x and y overlap", who);
-    const bool vec = C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0
-                     && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0;
-    const int CV = vec ? C / 4 : C, lpr = ln_lanes(CV), passes = (CV + lpr - 1) / lpr;
-    const long long groups = (nrows + 256 / lpr - 1) / (256 / lpr);
-    const dim3 grid((unsigned)(groups < LN_MAX_GROUPS ? groups : LN_MAX_GROUPS)), block(256);
+    LC_CHECK_ARG(!rs_overlap(x, ldx, nrows, C, y, ldy, nrows, C), "%s: x and y overlap", who);
+    const bool vec = rs_vec16(C, {ldx, ldy}, {x, y, gamma, beta});
+    const int CV = vec ? C / 4 : C, lpr = rs_lanes_fewest_idle(CV, 4, 64), passes = (CV + lpr - 1) / lpr;
+    const dim3 grid(rs_grid(nrows, 256 / lpr, LN_MAX_GROUPS)), block(256);
     hipStream_t s = (hipStream_t)stream;
 #define LC_LN(VW, L, NP) hipLaunchKernelGGL((ln_fwd_kernel<VW, L, NP>), grid, block, 0, s, x, (long long)ldx, gamma, beta, nrows, CV, \
                                             C, T, B, eps, seq_len, keep, 1.0f / keep, seed, stream0, drop_width, y, (long long)ldy)
-    if (vec) {
-        switch (lpr) {
-        case 4: LC_LN(4, 4, 8); break;
-        case 8: LC_LN(4, 8, 8); break;
-        case 16: LC_LN(4, 16, 8); break;
-        case 32: LC_LN(4, 32, 8); break;
-        default: if (passes <= 8) LC_LN(4, 64, 8); else LC_LN(4, 64, 32); break;
+    // below 64 lanes a lane holds at most 8 vectors; a whole wave holds the row however many passes that takes
+    rs_dispatch_lanes<4, 64>(lpr, [&](auto lanes) {
+        constexpr int L = decltype(lanes)::value;
+        if constexpr (L < 64) {
+            if (vec) LC_LN(4, L, 8); else LC_LN(1, L, 8);
+        } else if (vec) {
+            if (passes <= 8) LC_LN(4, 64, 8); else LC_LN(4, 64, 32);
+        } else {
+            if (passes <= 32) LC_LN(1, 64, 32); else LC_LN(1, 64, 128);
         }
-    } else {
-        switch (lpr) {
-        case 4: LC_LN(1, 4, 8); break;
-        case 8: LC_LN(1, 8, 8); break;
-        case 16: LC_LN(1, 16, 8); break;
-        case 32: LC_LN(1, 32, 8); break;
-        default: if (passes <= 32) LC_LN(1, 64, 32); else LC_LN(1, 64, 128); break;
-        }
-    }
+    });
 #undef LC_LN
     LC_CHECK_LAUNCH(who);
     return LC_OK;
@@ -340,8 +311,8 @@ extern "C" int lc_layer_norm_bwd(const float *x, int ldx, const float *dy, int l
     LC_CHECK_ARG(drop_width >= 1 && C % drop_width == 0, "%s: drop_width %d does not divide C %d", who, drop_width, C);
     const long long nrows = (long long)T * B;
     if (dx) {
-        LC_CHECK_ARG(!ln_overlap(x, ldx, nrows, dx, lddx, nrows, C), "%s: x and dx overlap", who);
-        LC_CHECK_ARG((dx == dy && lddx == lddy) || !ln_overlap(dy, lddy, nrows, dx, lddx, nrows, C),
+        LC_CHECK_ARG(!rs_overlap(x, ldx, nrows, C, dx, lddx, nrows, C), "%s: x and dx overlap", who);
+        LC_CHECK_ARG((dx == dy && lddx == lddy) || !rs_overlap(dy, lddy, nrows, C, dx, lddx, nrows, C),
                      "%s: dy and dx overlap (dx == dy with one pitch is the in-place form)", who);
     }
     if (dgamma) {
@@ -350,9 +321,8 @@ extern "C" int lc_layer_norm_bwd(const float *x, int ldx, const float *dy, int l
                      ln_workspace_bytes(nrows, C));
         LC_CHECK_ARG(dgamma != dbeta, "%s: dgamma and dbeta are one pointer", who);
     }
-    const bool vec = C % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && (!dx || lddx % 4 == 0)
-                     && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)gamma) & 15) == 0;
-    const int CV = vec ? C / 4 : C, lpr = ln_lanes(CV), passes = (CV + lpr - 1) / lpr;
+    const bool vec = rs_vec16(C, {ldx, lddy, dx ? lddx : 0}, {x, dy, dx, gamma});
+    const int CV = vec ? C / 4 : C, lpr = rs_lanes_fewest_idle(CV, 4, 64), passes = (CV + lpr - 1) / lpr;
     const bool wide = C > LN_REG_C;             // one wave per workgroup, its sums in LDS
     long long per;
     int nparts;
@@ -363,23 +333,17 @@ extern "C" int lc_layer_norm_bwd(const float *x, int ldx, const float *dy, int l
                                                            x, (long long)ldx, dy, (long long)lddy, gamma, nrows, CV, C, T, B, eps,     \
                                                            seq_len, keep, 1.0f / keep, seed, stream0, drop_width, dx,                 \
                                                            (long long)lddx, part, per)
-    if (vec) {
-        switch (lpr) {
-        case 4: LC_LN(4, 4, 8, 256, false); break;
-        case 8: LC_LN(4, 8, 8, 256, false); break;
-        case 16: LC_LN(4, 16, 8, 256, false); break;
-        case 32: LC_LN(4, 32, 8, 256, false); break;
-        default: if (passes <= 8) LC_LN(4, 64, 8, 256, false); else LC_LN(4, 64, 32, 64, true); break;
+    // as the forward; past LN_REG_C (more passes than the registers take) one wave per workgroup with its sums in LDS
+    rs_dispatch_lanes<4, 64>(lpr, [&](auto lanes) {
+        constexpr int L = decltype(lanes)::value;
+        if constexpr (L < 64) {
+            if (vec) LC_LN(4, L, 8, 256, false); else LC_LN(1, L, 8, 256, false);
+        } else if (vec) {
+            if (passes <= 8) LC_LN(4, 64, 8, 256, false); else LC_LN(4, 64, 32, 64, true);
+        } else {
+            if (passes <= 32) LC_LN(1, 64, 32, 256, false); else LC_LN(1, 64, 128, 64, true);
         }
-    } else {
-        switch (lpr) {
-        case 4: LC_LN(1, 4, 8, 256, false); break;
-        case 8: LC_LN(1, 8, 8, 256, false); break;
-        case 16: LC_LN(1, 16, 8, 256, false); break;
-        case 32: LC_LN(1, 32, 8, 256, false); break;
-        default: if (passes <= 32) LC_LN(1, 64, 32, 256, false); else LC_LN(1, 64, 128, 64, true); break;
-        }
-    }
+    });
 #undef LC_LN
     LC_CHECK_LAUNCH(who);
     if (dgamma) {

@@ -1,7 +1,7 @@
 // misc.hip — the bandwidth-bound helpers around the GEMMs: dropout scaling, column sums, transpose,
 // the packed-frame row gathers, the fused high-rank (MoE) head combine, the fused L2 + global-norm clip + optimizer update, and
 // the posterior transform of nnet-forward.  All are HBM-bound streaming kernels (no MFMA).
-#include "common.h"
+#include "row_stream.h"
 
 namespace {
 
@@ -358,68 +358,29 @@ __global__ __launch_bounds__(256) void label_smooth_kernel(const float *__restri
 
 // ------------------------------------------------------------------------------ packed frames
 // lc_pack_rows / lc_unpack_rows: out[r, :] = idx[r] >= 0 ? x[idx[r], :] : +0 for r < nrows - one gather by a row map, read in
-// either direction (packed row -> padded row, or padded row -> packed row).  Every output row is written exactly once, so
-// there is no memset beside it and nothing to order.  V = float4: 16-byte accesses (C, both pitches multiples of 4, aligned
-// bases); V = float: any C.  LPR lanes walk one row, 256 / LPR rows per workgroup pass; from LPR = 64 up a wave holds one row
-// and its map entry is ONE scalar load (the row number is made provably wave-uniform), below that each lane loads the entry of
-// its row once and keeps it over its columns.
-template <typename V, int LPR>
-__global__ __launch_bounds__(256) void gather_rows_kernel(const float *__restrict__ x, long long ldx, const int *__restrict__ idx,
-                                                          int nrows, int CV, float *__restrict__ out, long long ldo)
-{
-    constexpr int RPB = 256 / LPR;
-    const int lane = threadIdx.x % LPR, sub = threadIdx.x / LPR;
-    const int groups = (nrows + RPB - 1) / RPB;
-    for (int g = blockIdx.x; g < groups; g += gridDim.x) {
-        int r = g * RPB + sub;
-        if constexpr (LPR >= 64) r = __builtin_amdgcn_readfirstlane(r);
-        if (r >= nrows) continue;
-        const int src = idx[r];
-        V *dst = reinterpret_cast<V *>(out + (size_t)r * ldo);
-        if (src < 0) {
-            for (int q = lane; q < CV; q += LPR) dst[q] = V{};
-            continue;
-        }
-        const V *from = reinterpret_cast<const V *>(x + (size_t)src * ldx);
-        int q = lane;
-        for (; q + 3 * LPR < CV; q += 4 * LPR) {          // four loads in flight per lane before the first store
-            const V a = from[q], b = from[q + LPR], c = from[q + 2 * LPR], d = from[q + 3 * LPR];
-            dst[q] = a; dst[q + LPR] = b; dst[q + 2 * LPR] = c; dst[q + 3 * LPR] = d;
-        }
-        for (; q < CV; q += LPR) dst[q] = from[q];
-    }
-}
+// either direction (packed row -> padded row, or padded row -> packed row), on row_stream.h's skeleton: every output row is
+// written exactly once, so there is no memset beside it and nothing to order.  From LPR = 64 up a wave holds one row and its
+// map entry is ONE scalar load (the row number is made provably wave-uniform), below that each lane loads the entry of its row
+// once and keeps it over its columns.
+struct IndexMap {
+    static constexpr bool SUMS = false;
+    const int *idx;
 
-template <typename V>
-void launch_gather_rows(const float *x, int ldx, const int *idx, int nrows, int CV, float *out, int ldo, hipStream_t s)
-{
-    // lanes per row: the power of two that covers the row's elements, 4 .. 256; workgroups walk row groups with a grid
-    // stride, 8 resident per CU of 256 (a [51200, 4096] pack: 25 rows per workgroup)
-    int lpr = 4;
-    while (lpr < 256 && lpr < CV) lpr *= 2;
-    const int groups = lc_cdiv(nrows, 256 / lpr);
-    const dim3 grid((unsigned)(groups < 2048 ? groups : 2048)), block(256);
-#define LC_GATHER(L) hipLaunchKernelGGL((gather_rows_kernel<V, L>), grid, block, 0, s, x, (long long)ldx, idx, nrows, CV, out, (long long)ldo)
-    switch (lpr) {
-    case 4: LC_GATHER(4); break;
-    case 8: LC_GATHER(8); break;
-    case 16: LC_GATHER(16); break;
-    case 32: LC_GATHER(32); break;
-    case 64: LC_GATHER(64); break;
-    case 128: LC_GATHER(128); break;
-    default: LC_GATHER(256); break;
+    template <int LPR> __device__ __forceinline__ RsSpan locate(long long item, long long ldx, long long ldo) const
+    {
+        int r = (int)item;
+        if constexpr (LPR >= 64) r = __builtin_amdgcn_readfirstlane(r);
+        const int src = idx[r];
+        return {(long long)r * ldo, (long long)src * ldx, 0, src < 0 ? 0 : 1};
     }
-#undef LC_GATHER
-}
+};
 
 int gather_rows(const char *who, const float *x, int ldx, const int *idx, int nrows, int C, float *out, int ldo, lc_stream_t stream)
 {
     LC_CHECK_ARG(x && idx && out && nrows >= 0 && C > 0 && ldx >= C && ldo >= C, "%s: bad argument", who);
     if (nrows == 0) return LC_OK;
-    if (C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0)
-        launch_gather_rows<float4>(x, ldx, idx, nrows, C / 4, out, ldo, (hipStream_t)stream);
-    else
-        launch_gather_rows<float>(x, ldx, idx, nrows, C, out, ldo, (hipStream_t)stream);
+    // lanes per row: the power of two that covers the row's vectors (a [51200, 4096] pack: 25 rows per workgroup)
+    rs_launch_map(x, ldx, out, ldo, nrows, C, rs_lanes_cover, IndexMap{idx}, (hipStream_t)stream);
     LC_CHECK_LAUNCH(who);
     return LC_OK;
 }

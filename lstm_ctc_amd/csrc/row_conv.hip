@@ -4,14 +4,12 @@
 // [tau + 1, C].  Pure HBM streams: lanes along c, a thread produces ROWCONV_SEG consecutive frames of a fixed (b, c range) from
 // one walk over their tau + ROWCONV_SEG source rows - rows B * ld floats apart - so that a row is loaded (tau + 8) / 8 times,
 // not tau + 1 times, and the repeats are L2's.  Dead frames are never read.
-#include "common.h"
-#include <initializer_list>
+#include "row_stream.h"
 
 namespace {
 
 constexpr int ROWCONV_MAX_TAU = 32;      // design cap: a column group's weights fit in LDS (33 x 64 float4 = 33 KB)
 constexpr int ROWCONV_SEG = 8;           // consecutive frames one thread produces, their sums in registers
-constexpr int ROWCONV_MAX_GRID = 2048;   // workgroups of the row pass (8 per CU), the rest by grid stride
 constexpr int ROWCONV_SLABS = 512;       // row slabs of the dw reduction at most ...
 constexpr int ROWCONV_SLAB_ROWS = 64;    // ... of at least this many rows each
 constexpr int ROWCONV_JT = 8;            // kernel rows one dw workgroup accumulates
@@ -189,29 +187,16 @@ __global__ __launch_bounds__(256) void row_conv_dw_fold_kernel(const float *__re
     }
 }
 
-int rc_lanes(int CV)
-{
-    int lpr = 4;
-    while (lpr < 64 && lpr < CV) lpr *= 2;
-    return lpr;
-}
-
 template <typename V>
 void launch_rows(const float *x, int ldx, const float *w, int C, int CV, const RowConvArgs &a, float *out, int ldo, hipStream_t s)
 {
-    const int lpr = rc_lanes(CV);
+    const int lpr = rs_lanes_cover(CV, 4, 64);
     const long long items = (long long)lc_cdiv(a.T, ROWCONV_SEG) * a.B;
-    const long long groups = (items + 256 / lpr - 1) / (256 / lpr);
-    const dim3 grid((unsigned)lc_cdiv(CV, lpr), (unsigned)(groups < ROWCONV_MAX_GRID ? groups : ROWCONV_MAX_GRID)), block(256);
-#define LC_ROWCONV(L) hipLaunchKernelGGL((row_conv_rows_kernel<V, L>), grid, block, 0, s, x, (long long)ldx, w, C, CV, items, a, out, (long long)ldo)
-    switch (lpr) {
-    case 4: LC_ROWCONV(4); break;
-    case 8: LC_ROWCONV(8); break;
-    case 16: LC_ROWCONV(16); break;
-    case 32: LC_ROWCONV(32); break;
-    default: LC_ROWCONV(64); break;
-    }
-#undef LC_ROWCONV
+    const dim3 grid((unsigned)lc_cdiv(CV, lpr), rs_grid(items, 256 / lpr)), block(256);
+    rs_dispatch_lanes<4, 64>(lpr, [&](auto L) {
+        hipLaunchKernelGGL((row_conv_rows_kernel<V, decltype(L)::value>), grid, block, 0, s, x, (long long)ldx, w, C, CV, items, a,
+                           out, (long long)ldo);
+    });
 }
 
 int rc_slabs(long long rows)
@@ -224,20 +209,15 @@ template <typename V>
 void launch_dw(const float *x, int ldx, const float *dy, int lddy, int C, int CV, const RowConvArgs &a, float *part, float *dw,
                hipStream_t s)
 {
-    const int lpr = rc_lanes(CV);
+    const int lpr = rs_lanes_cover(CV, 4, 64);
     const long long rows = (long long)a.T * a.B;
     const long long slab_rows = (rows + rc_slabs(rows) - 1) / rc_slabs(rows);
     const int nslab = (int)((rows + slab_rows - 1) / slab_rows);        // no empty slab
     const dim3 grid((unsigned)lc_cdiv(CV, lpr), (unsigned)nslab, (unsigned)lc_cdiv(a.tau + 1, ROWCONV_JT)), block(256);
-#define LC_ROWCONV(L) hipLaunchKernelGGL((row_conv_dw_partial_kernel<V, L>), grid, block, 0, s, x, (long long)ldx, dy, (long long)lddy, C, CV, rows, slab_rows, a, part)
-    switch (lpr) {
-    case 4: LC_ROWCONV(4); break;
-    case 8: LC_ROWCONV(8); break;
-    case 16: LC_ROWCONV(16); break;
-    case 32: LC_ROWCONV(32); break;
-    default: LC_ROWCONV(64); break;
-    }
-#undef LC_ROWCONV
+    rs_dispatch_lanes<4, 64>(lpr, [&](auto L) {
+        hipLaunchKernelGGL((row_conv_dw_partial_kernel<V, decltype(L)::value>), grid, block, 0, s, x, (long long)ldx, dy,
+                           (long long)lddy, C, CV, rows, slab_rows, a, part);
+    });
     const long long n = (long long)(a.tau + 1) * C;
     hipLaunchKernelGGL(row_conv_dw_fold_kernel, dim3((unsigned)((n + ROWCONV_FOLD_E - 1) / ROWCONV_FOLD_E)), dim3(256), 0, s, part,
                        nslab, n, dw);
@@ -247,22 +227,13 @@ void launch_dw(const float *x, int ldx, const float *dy, int lddy, int C, int CV
 // bases less than a pitch apart modulo it, C apart at least) interleave without touching.
 bool rc_overlap(const float *a, long long lda, const float *b, long long ldb, long long rows, int C)
 {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + ((rows - 1) * lda + C) * sizeof(float);
-    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + ((rows - 1) * ldb + C) * sizeof(float);
-    if (a1 <= b0 || b1 <= a0) return false;
+    if (!rs_overlap(a, lda, rows, C, b, ldb, rows, C)) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     if (lda == ldb && (a0 > b0 ? a0 - b0 : b0 - a0) % sizeof(float) == 0) {
         const uintptr_t lo = a0 < b0 ? a0 : b0, hi = a0 < b0 ? b0 : a0;
         const long long d = (long long)(((hi - lo) / sizeof(float)) % (uintptr_t)lda);
         if (d >= C && d + C <= lda) return false;
     }
-    return true;
-}
-
-bool rc_vec(int C, std::initializer_list<long long> pitches, std::initializer_list<const void *> bases)
-{
-    if (C % 4) return false;
-    for (long long p : pitches) if (p % 4) return false;
-    for (const void *b : bases) if ((uintptr_t)b & 15) return false;
     return true;
 }
 
@@ -287,7 +258,7 @@ extern "C" int lc_row_conv_fwd(const float *x, int ldx, const float *w, int T, i
     RowConvArgs a;
     a.T = T; a.B = B; a.tau = tau; a.fwd = 1; a.seq_len = seq_len;
     hipStream_t s = (hipStream_t)stream;
-    if (rc_vec(C, {ldx, ldy}, {x, w, y}))
+    if (rs_vec16(C, {ldx, ldy}, {x, w, y}))
         launch_rows<float4>(x, ldx, w, C, C / 4, a, y, ldy, s);
     else
         launch_rows<float>(x, ldx, w, C, C, a, y, ldy, s);
@@ -316,13 +287,13 @@ extern "C" int lc_row_conv_bwd(const float *x, int ldx, const float *dy, int ldd
     a.T = T; a.B = B; a.tau = tau; a.fwd = 0; a.seq_len = seq_len;
     hipStream_t s = (hipStream_t)stream;
     if (dx) {
-        if (rc_vec(C, {lddy, lddx}, {dy, w, dx}))
+        if (rs_vec16(C, {lddy, lddx}, {dy, w, dx}))
             launch_rows<float4>(dy, lddy, w, C, C / 4, a, dx, lddx, s);
         else
             launch_rows<float>(dy, lddy, w, C, C, a, dx, lddx, s);
     }
     if (dw) {
-        if (rc_vec(C, {ldx, lddy}, {x, dy, workspace}))
+        if (rs_vec16(C, {ldx, lddy}, {x, dy, workspace}))
             launch_dw<float4>(x, ldx, dy, lddy, C, C / 4, a, (float *)workspace, dw, s);
         else
             launch_dw<float>(x, ldx, dy, lddy, C, C, a, (float *)workspace, dw, s);

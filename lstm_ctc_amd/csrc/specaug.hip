@@ -18,7 +18,7 @@
 // are taken once per thread, outside the row loop (rows wider than the 256 lanes of a workgroup divide on the fly).
 // Measured (profiles/specaug_probe.txt): the first version tested every element against the pairs, one dependent LDS read per
 // pair - 2.0 x a device copy at [1000, 64, 360]; the one-word form is what the file records now.
-#include "common.h"
+#include "row_stream.h"
 #include <math.h>
 
 namespace {
@@ -210,20 +210,13 @@ void launch_spec_augment(const float *x, int ldx, long long nrows, int B, int CV
                          float *out, int ldo, int *plan, hipStream_t s)
 {
     // lanes per row: the power of two that covers the row's vectors, 16 .. 256 (16 threads per row build its masks); 4 rows
-    // per lane and pass; at most 2048 workgroups, the rest by grid stride
-    int lpr = 16;
-    while (lpr < 256 && lpr < CV) lpr *= 2;
-    const long long groups = (nrows + (256 / lpr) * 4 - 1) / ((256 / lpr) * 4);
-    const dim3 grid((unsigned)(groups < 2048 ? groups : 2048)), block(256);
-#define LC_SPEC(L) hipLaunchKernelGGL((spec_augment_kernel<V, L, BITS>), grid, block, 0, s, x, (long long)ldx, nrows, B, CV, seq_len, a, out, (long long)ldo, plan)
-    switch (lpr) {
-    case 16: LC_SPEC(16); break;
-    case 32: LC_SPEC(32); break;
-    case 64: LC_SPEC(64); break;
-    case 128: LC_SPEC(128); break;
-    default: LC_SPEC(256); break;
-    }
-#undef LC_SPEC
+    // per lane and pass
+    const int lpr = rs_lanes_cover(CV, 16, 256);
+    const dim3 grid(rs_grid(nrows, (256 / lpr) * 4)), block(256);
+    rs_dispatch_lanes<16, 256>(lpr, [&](auto L) {
+        hipLaunchKernelGGL((spec_augment_kernel<V, decltype(L)::value, BITS>), grid, block, 0, s, x, (long long)ldx, nrows, B, CV,
+                           seq_len, a, out, (long long)ldo, plan);
+    });
 }
 
 }  // namespace
@@ -256,7 +249,7 @@ extern "C" int lc_spec_augment(const float *x, int T, int B, int D, int ldx, con
     a.nb = 1 + cfg->left_context + cfg->right_context;
     a.fill = cfg->fill; a.seed = seed;
     const long long nrows = (long long)T * B;
-    const bool vec = D % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
+    const bool vec = rs_vec16(D, {ldx, ldo}, {x, out});
     const bool bits = a.nb <= 32 && a.F <= 64;          // a row's masks fit one LDS word: a bit per block, a bit per bin
     hipStream_t s = (hipStream_t)stream;
     if (vec && bits) launch_spec_augment<float4, true>(x, ldx, nrows, B, D / 4, seq_len, a, out, ldo, plan, s);

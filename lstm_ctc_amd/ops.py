@@ -793,16 +793,14 @@ def length_mask_(x, seq_len, T, B):
 def _gather_rows(fn, x, index, out):
     lib = _lib.load()
     _require_cuda(x, index, out)
-    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
+    _check_rows(x)
     assert index.dim() == 1 and index.dtype == torch.int32 and index.is_contiguous()
     n, C = index.shape[0], x.shape[1]
     if out is None:
         out = torch.empty((n, C), dtype=torch.float32, device=x.device)
-    assert out.dim() == 2 and out.shape == (n, C) and out.dtype == torch.float32 and out.stride(1) == 1
-    ldx = x.stride(0) if x.shape[0] > 1 else max(x.stride(0), C)
-    ldo = out.stride(0) if n > 1 else max(out.stride(0), C)
+    _check_rows(out, n, C)
     ev = _prof_begin()
-    _lib.check(getattr(lib, fn)(_ptr(x), ldx, _ptr(index), n, C, _ptr(out), ldo, _stream()), fn)
+    _lib.check(getattr(lib, fn)(_ptr(x), _rows_pitch(x, C), _ptr(index), n, C, _ptr(out), _rows_pitch(out, C), _stream()), fn)
     _prof_end("pack", 8.0 * n * C, ev)           # bytes moved when every row has a source: 4 read + 4 written
     return out
 
@@ -842,6 +840,17 @@ def _rows_pitch(t, C):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), C)
 
 
+def _check_rows(m, rows=None, C=None):
+    """What every row pass asks of a matrix: a 2-D fp32 view, last stride 1, of this shape (None: any)."""
+    assert m.dim() == 2 and m.dtype == torch.float32 and m.stride(1) == 1 and (rows is None or m.shape[0] == rows) \
+        and (C is None or m.shape[1] == C), (tuple(m.shape), m.stride(), (rows, C))
+
+
+def _check_lengths(seq_len, B):
+    """... and of the lengths: int32, contiguous, one per utterance."""
+    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+
+
 def chunk_gather(x, T, B, chunk, lookahead, zero_lookahead=False, out=None):
     """Padded -> chunked (lc_chunk_gather): x [T*B, C] time-major f32 (a 2-D view, last stride 1) -> out [Tc*Bc, C],
     out[tau * Bc + c * B + b] = x[(c * chunk + tau) * B + b] where that frame exists (and, with zero_lookahead, tau < chunk),
@@ -849,11 +858,11 @@ def chunk_gather(x, T, B, chunk, lookahead, zero_lookahead=False, out=None):
     lib = _lib.load()
     _require_cuda(x, out)
     _, Tc, Bc = chunk_shape(T, B, chunk, lookahead)
-    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1 and x.shape[0] == T * B, (x.shape, x.stride())
+    _check_rows(x, T * B)
     C = x.shape[1]
     if out is None:
         out = torch.empty((Tc * Bc, C), dtype=torch.float32, device=x.device)
-    assert out.dim() == 2 and tuple(out.shape) == (Tc * Bc, C) and out.dtype == torch.float32 and out.stride(1) == 1
+    _check_rows(out, Tc * Bc, C)
     ev = _prof_begin()
     _lib.check(lib.lc_chunk_gather(_ptr(x), _rows_pitch(x, C), T, B, C, int(chunk), int(lookahead), int(bool(zero_lookahead)),
                                    _ptr(out), _rows_pitch(out, C), _stream()), "lc_chunk_gather")
@@ -868,13 +877,13 @@ def chunk_fold(xc, T, B, chunk, lookahead, sum_copies=False, seq_len=None, out=N
     lib = _lib.load()
     _require_cuda(xc, seq_len, out)
     _, Tc, Bc = chunk_shape(T, B, chunk, lookahead)
-    assert xc.dim() == 2 and xc.dtype == torch.float32 and xc.stride(1) == 1 and xc.shape[0] == Tc * Bc, (xc.shape, xc.stride())
+    _check_rows(xc, Tc * Bc)
     C = xc.shape[1]
     if seq_len is not None:
-        assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+        _check_lengths(seq_len, B)
     if out is None:
         out = torch.empty((T * B, C), dtype=torch.float32, device=xc.device)
-    assert out.dim() == 2 and tuple(out.shape) == (T * B, C) and out.dtype == torch.float32 and out.stride(1) == 1
+    _check_rows(out, T * B, C)
     ev = _prof_begin()
     _lib.check(lib.lc_chunk_fold(_ptr(xc), _rows_pitch(xc, C), T, B, C, int(chunk), int(lookahead), int(bool(sum_copies)),
                                  _ptr(seq_len), _ptr(out), _rows_pitch(out, C), _stream()), "lc_chunk_fold")
@@ -889,10 +898,9 @@ ROW_CONV_MAX_TAU = 32       # the library's design cap (include/lstm_ctc_hip.h)
 def _row_conv_args(w, seq_len, T, B, *mats):
     assert w.dim() == 2 and w.dtype == torch.float32 and w.is_contiguous(), (w.shape, w.stride())
     tau, C = w.shape[0] - 1, w.shape[1]
-    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+    _check_lengths(seq_len, B)
     for m in mats:
-        assert m.dim() == 2 and m.dtype == torch.float32 and m.stride(1) == 1 and tuple(m.shape) == (T * B, C), \
-            (tuple(m.shape), m.stride(), (T * B, C))
+        _check_rows(m, T * B, C)
     return tau, C
 
 
@@ -972,10 +980,9 @@ def _time_reduce_args(seq_len, T, B, C, r, narrow, wide):
     if not (TIME_REDUCE_MIN_FACTOR <= int(r) <= TIME_REDUCE_MAX_FACTOR):
         raise ValueError("time reduction: r must be in %d..%d, got %r" % (TIME_REDUCE_MIN_FACTOR, TIME_REDUCE_MAX_FACTOR, r))
     To = time_reduce_frames(T, r)
-    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
-    for m, shape in ((narrow, (T * B, C)), (wide, (To * B, r * C))):
-        assert m.dim() == 2 and m.dtype == torch.float32 and m.stride(1) == 1 and tuple(m.shape) == shape, \
-            (tuple(m.shape), m.stride(), shape)
+    _check_lengths(seq_len, B)
+    _check_rows(narrow, T * B, C)
+    _check_rows(wide, To * B, r * C)
     return To
 
 
@@ -1019,18 +1026,18 @@ def time_reduce_bwd(dy2d, seq_len, T, B, r, out=None):
 # ------------------------------------------------------------------------------------------ layer normalisation
 LN_EPS = 1e-5               # one constant, like BN_EPS
 LAYER_NORM_MAX_C = 8192     # the library's cap: a row lives in one wave's registers (include/lstm_ctc_hip.h)
-# csrc/layer_norm.hip's launch constants (LN_MAX_GROUPS; 256 threads over rows of at least 4 lanes): more rows than their product
+# csrc/layer_norm.hip's launch constants (LN_MAX_GROUPS, its cap for row_stream.h's rs_grid; 256 threads over rows of at least 4
+# lanes): more rows than their product
 # and every lane choice's launch walks its rows in more than one pass, and the backward leaves more than one partial per column
 LAYER_NORM_MAX_GROUPS, LAYER_NORM_MAX_ROWS_PER_GROUP = 1024, 64
 
 
 def _layer_norm_args(C, seq_len, T, B, keep, drop_width, vecs, *mats):
-    assert seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.numel() == B
+    _check_lengths(seq_len, B)
     for v in vecs:
         assert v.dim() == 1 and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == C, (tuple(v.shape), C)
     for m in mats:
-        assert m.dim() == 2 and m.dtype == torch.float32 and m.stride(1) == 1 and tuple(m.shape) == (T * B, C), \
-            (tuple(m.shape), m.stride(), (T * B, C))
+        _check_rows(m, T * B, C)
     if not 1 <= C <= LAYER_NORM_MAX_C:
         raise ValueError("layer normalisation: C must be in 1..%d, got %d" % (LAYER_NORM_MAX_C, C))
     if not 0.0 < keep <= 1.0:

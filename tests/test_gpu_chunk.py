@@ -22,6 +22,10 @@ CASES = [
     (7, 2, 6, 3, 1, 3),            # pitches C + 3: scalar path
     (5, 300, 8, 2, 1, 0),          # Bc = 900 rows
     (11, 4, 64, 4, 9, 0),          # B = 4: the four kinds of length side by side (seq_len tests)
+    # every path of csrc/row_stream.h's map_rows_kernel through the chunk maps
+    (5, 2, 4100, 2, 1, 0),         # 1025 float4 per row on 256 lanes: the four-in-flight copy loop and its remainder
+    (5, 2, 1030, 2, 1, 3),         # the same through the scalar path
+    (4, 33000, 8, 2, 1, 0),        # 198000 gathered / 132000 folded rows at 4 lanes: RS_MAX_GROUPS * 64 = 131072 rows per sweep
 ]
 IDS = ["T%d_B%d_C%d_Nc%d_Nr%d_pad%d" % c for c in CASES]
 

@@ -32,8 +32,8 @@ CASES = [
     (5, 300, 8, 1, 0),             # many narrow rows
     (40, 5, 16, 32, 0),            # tau at the cap
     # The launcher's constants (csrc/row_conv.hip): C = 4 is one vector, so 4 lanes per item and 64 items per workgroup pass;
-    # an item is ROWCONV_SEG = 8 frames of one utterance, so T = 3 gives B items; ROWCONV_MAX_GRID = 2048 workgroups take
-    # 2048 * 64 = 131072 items in one pass - 132000 need the grid stride.  The 396000 rows cap at ROWCONV_SLABS = 512 dw slabs
+    # an item is ROWCONV_SEG = 8 frames of one utterance, so T = 3 gives B items; csrc/row_stream.h's RS_MAX_GROUPS = 2048
+    # workgroups take 2048 * 64 = 131072 items in one pass - 132000 need the grid stride.  The 396000 rows cap at ROWCONV_SLABS = 512 dw slabs
     # of ceil(396000 / 512) = 774 rows, the last one with 486.
     (3, 132000, 4, 2, 0),
 ]

@@ -16,7 +16,7 @@ import time_reduce_reference as ref  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -77.25
-GRID_CAP = 2048                      # csrc/time_reduce.hip: TR_MAX_GROUPS workgroups, the rest by grid stride
+GRID_CAP = 2048                      # csrc/row_stream.h: RS_MAX_GROUPS workgroups, the rest by grid stride
 SEGMENTS_PER_WORKGROUP_AT_C4 = 64    # 256 threads / 4 lanes per segment, the narrowest row
 ONE_SWEEP = GRID_CAP * SEGMENTS_PER_WORKGROUP_AT_C4      # 131072 segments: more than this and workgroups take a second stride
 
@@ -94,7 +94,8 @@ SHAPES = {   # name -> (T, B, C, r)
     "T_below_r_2": (1, 8, 4, 2),
     "T_below_r_4": (3, 8, 4, 4),
     "C1": (7, 8, 1, 2),
-    "C1028": (5, 8, 1028, 2),           # 257 vectors: more than a workgroup's 256 lanes
+    "C1028": (5, 8, 1028, 2),           # 257 vectors: more than a workgroup's 256 lanes (64 lanes by the fewest-idle rule)
+    "C4100": (3, 8, 4100, 2),           # 1025 vectors: 256 lanes, five passes - the four-in-flight copy loop and its remainder
     "B3": (7, 3, 5, 2),                 # the issue's shapes at their own B: the lengths are cut to the first B of the list
     "B4": (8, 4, 8, 2),
     "B2": (10, 2, 12, 3),
