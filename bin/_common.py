@@ -381,6 +381,20 @@ def report_layer_norm(nnet_config):
         tflog.info(line)
 
 
+def report_conv(nnet_config):
+    """One INFO line when <nnet-config> sets conv_layers (the convolutional front-end): layers, channels, bins
+    per layer, the width layer 0 reads and the parameters added.  A config the model refuses (a spliced input, use_bn,
+    pack_frames, a compute_dtype other than fp32, bad values): the FATAL line and exit 1, before a model is built."""
+    from lstm_ctc_amd.nnet.model import conv_info_line
+    try:
+        line = conv_info_line(nnet_config)
+    except ValueError as exc:
+        _fatal(str(exc))
+    if line:
+        from lstm_ctc_amd.nnet import tflog
+        tflog.info(line)
+
+
 def report_time_reduce(nnet_config, args=None, aligning=False):
     """One INFO line when <nnet-config> sets time_reduce_layers (the pyramidal BiLSTM): the layers, r, R and how
     many model and raw frames one frame of the logits stands for.  A config the model refuses, or (``args``) a command line

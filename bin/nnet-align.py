@@ -6,7 +6,7 @@ scp order.  An utterance without labels, or whose labels do not fit its frames, 
 import os
 import sys
 
-from _common import build_cli, setup_device, report_chunking, report_row_conv, report_layer_norm, report_time_reduce, star_report_keywords, star_report_line
+from _common import build_cli, setup_device, report_chunking, report_row_conv, report_layer_norm, report_conv, report_time_reduce, star_report_keywords, star_report_line
 
 
 def main(args):
@@ -26,6 +26,7 @@ def main(args):
     report_chunking(nnet_config)                          # chunk_frames / lookahead_frames: one INFO line
     report_row_conv(nnet_config)                          # row_conv_frames: one INFO line
     report_layer_norm(nnet_config)                        # layer_norm: one INFO line
+    report_conv(nnet_config)                              # conv_layers: one INFO line
     report_time_reduce(nnet_config, aligning=True)        # time_reduce_layers: fatal, alignments are per input frame
     filename, tfrecord, _ = nnet.dataset_from_tfrecords(
         tfrecords_scp=args.tfrecords_scp, left_context=nnet_config.get('left_context'),

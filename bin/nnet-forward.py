@@ -6,7 +6,7 @@ to one-at-a-time runs because padding is masked, and are written in scp order.""
 import os
 import sys
 
-from _common import build_cli, setup_device, report_chunking, report_row_conv, report_layer_norm, report_time_reduce
+from _common import build_cli, setup_device, report_chunking, report_row_conv, report_layer_norm, report_conv, report_time_reduce
 
 
 def main(args):
@@ -23,6 +23,7 @@ def main(args):
     report_chunking(nnet_config)                          # chunk_frames / lookahead_frames: one INFO line
     report_row_conv(nnet_config)                          # row_conv_frames: one INFO line
     report_layer_norm(nnet_config)                        # layer_norm: one INFO line
+    report_conv(nnet_config)                              # conv_layers: one INFO line
     report_time_reduce(nnet_config)                       # time_reduce_layers: one INFO line
     if args.apply_log:
         args.apply_softmax = True

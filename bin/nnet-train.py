@@ -7,7 +7,7 @@ import sys
 from _common import (build_cli, setup_device, quiet_unless_rank0, read_frame_targets, report_frame_targets,
                      report_label_windows, read_teacher_scores, teacher_keywords, report_teacher_scores, criterion_keywords,
                      report_criterion, spec_augment_keywords, report_spec_augment, consistency_keywords, report_consistency,
-                     report_chunking, report_row_conv, report_layer_norm, report_time_reduce, report_time_reduce_short)
+                     report_chunking, report_row_conv, report_layer_norm, report_conv, report_time_reduce, report_time_reduce_short)
 
 
 def main(args):
@@ -26,6 +26,7 @@ def main(args):
         report_chunking(nnet_config)                      # chunk_frames / lookahead_frames: one INFO line
         report_row_conv(nnet_config)                      # row_conv_frames: one INFO line
         report_layer_norm(nnet_config)                    # layer_norm: one INFO line
+        report_conv(nnet_config)                          # conv_layers: one INFO line
         report_time_reduce(nnet_config, args)             # time_reduce_layers: one INFO line; fatal with a frame-rate table
         nnet_type = nnet_config.get('nnet_type')
         filename, tfrecord, input_dim = nnet.dataset_from_tfrecords(

@@ -745,6 +745,47 @@ int lc_layer_norm_bwd(const float *x, int ldx, const float *dy, int lddy, const 
                       float *dx /* or NULL */, int lddx, float *dgamma, float *dbeta /* both or neither; overwritten */,
                       void *workspace, size_t workspace_bytes, lc_stream_t stream);
 
+/* ------------------------------------------------------------------ convolutional front-end - */
+/* One layer of the 2-D convolutional front-end between the features and the first LSTM layer (Deep Speech 2, VGG-BLSTM; no
+ * reference counterpart): kernel 3 (time) x 3 (frequency), time stride 1, frequency stride 2, zero padding 1 on
+ * every side, bias and ReLU fused - torch.nn.functional.conv2d(padding=1, stride=(1, 2)) + relu with the dead-frame rule.
+ * x / dx are time-major [T * B, Cin * F] with row pitches ldx / lddx in floats; with x_group_major != 0 column ci * F + f (the
+ * loader's layout: statics, deltas and delta-deltas as blocks of F bins), otherwise column f * Cin + ci (what a previous
+ * layer writes).  y / dy are [T * B, Fo * Cout], column fo * Cout + co, Fo = ceil(F / 2), pitches ldy / lddy.  w / dw are dense
+ * [3, 3, Cin, Cout] (time tap i, bin tap j, in, out), bias / dbias dense [Cout]; seq_len is a device [B] int32 and is REQUIRED.
+ * With len_b = clamp(seq_len[b], 0, T), live(t, b) = t < len_b, xz = x on live frames and bins 0 .. F - 1 and 0 everywhere else
+ * (those elements are never read), and g = dy where y > 0, else 0:
+ *   lc_conv_fwd   y[t,b,fo,co]   = relu(bias[co] + sum_{i,j,ci} w[i,j,ci,co] * xz[t+i-1, b, 2fo+j-1, ci])       if live, else +0
+ *   lc_conv_bwd   dx[t,b,f,ci]   = sum over (i, j, fo, co) with live(t-i+1, b) and 2fo+j-1 == f of
+ *                                  w[i,j,ci,co] * g[t-i+1,b,fo,co]                                             if live, else +0
+ *                 dw[i,j,ci,co]  = sum over b, live t, fo of g[t,b,fo,co] * xz[t+i-1,b,2fo+j-1,ci]
+ *                 dbias[co]      = sum over b, live t, fo of g[t,b,fo,co]                                      (both overwritten)
+ *   - Three direct convolutions on fp32 FMAs over LDS tiles: a workgroup stages a segment of frames with one halo row on each
+ *     side, so a row is fetched once per segment and not once per tap, and 8 channels of the reduction at a time.
+ *   - Dead rows of x, y and dy are never read (NaN included) and written +0; neighbouring utterances never leak into each other
+ *     (rows t - 1 and t + 1 are the SAME utterance's); every element of every non-NULL output is written on every successful
+ *     call, and nothing outside the windows is touched.
+ *   - Determinism: no atomics.  Each workgroup of the weight gradient walks a fixed, contiguous share of the tiles and leaves
+ *     one [9 Cin Cout + Cout] partial in the workspace; a second kernel adds the partials in a fixed order.  The same call
+ *     gives the same bits.
+ *   - Pointers: dx may be NULL (the first layer); dw and dbias are both NULL or both not; not all three.  x is needed for dw
+ *     only, the workspace too.
+ *   - Elements are indexed in 64 bits.  y (and a channel-minor dx with Cin a multiple of 4) are written with 16-byte stores,
+ *     and the weight gradient reads y and dy with 16-byte loads, when the pitches are multiples of 4 floats and the bases
+ *     16-byte aligned; the scalar path otherwise, and for every other access.
+ * LC_EINVAL, with nothing launched and no output touched: T, B, F, Cin, Cout <= 0; Cin > 64, Cout > 64, Cout not a multiple of
+ * 8 or F > 512 (design caps: a workgroup's weight chunk and partial live in LDS, a thread owns 4 output channels); a NULL
+ * required pointer; one of dw / dbias alone; all three gradient outputs NULL; a pitch below its row; an output window that
+ * overlaps an input window or another output.  LC_EWORKSPACE: a non-NULL dw with a workspace below lc_conv_workspace_bytes
+ * (0 for a bad shape). */
+size_t lc_conv_workspace_bytes(int T, int B, int F, int Cin, int Cout);
+int lc_conv_fwd(const float *x, int ldx, int x_group_major, const float *w, const float *bias,
+                int T, int B, int F, int Cin, int Cout, const int *seq_len, float *y, int ldy, lc_stream_t stream);
+int lc_conv_bwd(const float *x, int ldx, int x_group_major, const float *y, int ldy, const float *dy, int lddy,
+                const float *w, int T, int B, int F, int Cin, int Cout, const int *seq_len,
+                float *dx /* or NULL */, int lddx, float *dw, float *dbias /* both or neither; overwritten */,
+                void *workspace, size_t workspace_bytes, lc_stream_t stream);
+
 /* ------------------------------------------------------------------ SpecAugment ------------- */
 /* Time and frequency masking of the filterbank input (Park et al., 2019; no reference counterpart), on the spliced and
  * subsampled batch the loader uploads.  x and out are time-major [T * B, D] with row pitches ldx / ldo (floats); out == x (in

@@ -98,6 +98,11 @@ SIGNATURES = {
                                   c_u32, c_int, c_void_p, c_int, c_void_p]),
     "lc_layer_norm_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_float,
                                   c_u32, c_u32, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lc_conv_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "lc_conv_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                            c_int, c_void_p]),
+    "lc_conv_bwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                            c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "lc_spec_augment": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_u32, c_void_p, c_int, c_void_p,
                                 c_void_p]),
     "lc_lstm_fwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -17,7 +17,7 @@ void lc_set_error(const char *fmt, ...)
 }
 
 extern "C" const char *lc_last_error(void) { return g_err; }
-extern "C" int lc_version(void) { return 14; }     // 14: lc_layer_norm_fwd / lc_layer_norm_bwd, 13: lc_time_reduce_fwd / lc_time_reduce_bwd, 2: lc_pack_rows / lc_unpack_rows, 3: lc_xent_loss, 4: lc_ctc_loss_windowed, 5: lc_kd_loss, 6: lc_ctc_loss_delay, 7: lc_spec_augment, 8: lc_consistency_loss, 9: lc_chunk_gather / lc_chunk_fold, 10: lc_ctc_loss_entropy, 11: lc_ctc_loss_star, 12: lc_row_conv_fwd / lc_row_conv_bwd
+extern "C" int lc_version(void) { return 15; }     // 15: lc_conv_fwd / lc_conv_bwd, 14: lc_layer_norm_fwd / lc_layer_norm_bwd, 13: lc_time_reduce_fwd / lc_time_reduce_bwd, 2: lc_pack_rows / lc_unpack_rows, 3: lc_xent_loss, 4: lc_ctc_loss_windowed, 5: lc_kd_loss, 6: lc_ctc_loss_delay, 7: lc_spec_augment, 8: lc_consistency_loss, 9: lc_chunk_gather / lc_chunk_fold, 10: lc_ctc_loss_entropy, 11: lc_ctc_loss_star, 12: lc_row_conv_fwd / lc_row_conv_bwd
 
 // ---- development switches -------------------------------------------------------------------------------------------
 // Every switch has ONE reader, lc_option(): a per-thread override set through lc_set_option() wins, then the LC_*

@@ -18,7 +18,8 @@ MI355X-first design choices:
   kernel wants; TF's ``[i|j|f|o]`` layout only exists at checkpoint I/O (:meth:`ParamStore.export_tf`);
 * all parameters (and gradients, and optimizer slots) are single flat fp32 buffers: L2-decayed
   tensors first, the LSTM ``bias`` vectors (the only names containing "bias", nnet/graph.py:185) last - and behind them, with
-  ``layer_norm``, the gains and offsets ``ln{i}/gamma``, ``ln{i}/beta``, undecayed by kind.
+  ``layer_norm``, the gains and offsets ``ln{i}/gamma``, ``ln{i}/beta``, undecayed by kind.  The convolutional front-end's
+  ``conv{k}/kernel`` lie behind the LSTM layers' decayed tensors, its ``conv{k}/bias`` behind the LSTM biases.
 """
 import math
 import os
@@ -71,16 +72,21 @@ class ParamStore:
         # pyramidal BiLSTM (extension keys time_reduce_layers / time_reduce_factor): a reduced layer reads r
         # frames of the layer below side by side - its kernels are r times as tall in their input part, nothing else moves
         self.time_reduce, self.time_reduce_factor = time_reduce_config(cfg)
+        # convolutional front-end (extension keys conv_layers / conv_channels / conv_bins): layer 0 reads the
+        # last conv layer's [F_n * Cc] columns where it read the D input columns - its kernel is that tall, nothing else moves
+        self.conv = conv_config(cfg)
+        self.D0 = self.conv[-1][3] * self.conv[-1][1] if self.conv else D
+        D0 = self.D0
         specs = []       # (name, shape, kind)
         for i in range(self.num_layers):
             if self.blstm:
-                I = D if i == 0 else (self.time_reduce_factor if i in self.time_reduce else 1) * 2 * self.Pout
+                I = D0 if i == 0 else (self.time_reduce_factor if i in self.time_reduce else 1) * 2 * self.Pout
                 prefixes = ["fd%d/frnn%d" % (i, i), "bd%d/brnn%d" % (i, i)]       # bilstm.py:135,156,178,187
             elif self.cudnn:
-                I = D if i == 0 else N
+                I = D0 if i == 0 else N
                 prefixes = [CUDNN_CELL % i]                                        # lstm.py:73-88 (MultiRNNCell scopes)
             else:
-                I = D if i == 0 else self.Pout
+                I = D0 if i == 0 else self.Pout
                 prefixes = ["drnn%d/lstm_cell" % i]                                # lstm.py:279-287
             for pre in prefixes:
                 specs.append((pre + "/kernel", (I + self.Pout, 4 * N), "lstm_kernel"))
@@ -106,6 +112,11 @@ class ParamStore:
         self.row_conv = row_conv_config(cfg)
         if self.row_conv:
             specs.append(("row_conv/kernel", (self.row_conv + 1, H), "row_conv"))
+        # the front-end's layers: behind the LSTM layers' tensors too (layer_grad_range and the data-parallel buckets keep their
+        # ranges; these gradients are the last to become ready and go out with GradientBuckets.finish()).  The kernels are
+        # L2-decayed, the biases undecayed through the "bias" in their names
+        for k, (Cin, Cc, _, _) in enumerate(self.conv):
+            specs += [("conv%d/kernel" % k, (3, 3, Cin, Cc), "conv_kernel"), ("conv%d/bias" % k, (Cc,), "conv_bias")]
         # layer normalisation (extension key layer_norm): a gain and an offset per layer output.  Kept out of the
         # L2 decay by kind (a gain decayed towards zero is not wanted), so they lie with the biases behind every decayed tensor
         # and layer_grad_range and the data-parallel buckets keep their ranges
@@ -182,6 +193,13 @@ class ParamStore:
             raise KeyError("checkpoint has no %s: a model with layer_norm = true cannot start from a plain model's checkpoint "
                            "(no setting of ln*/gamma and ln*/beta computes what that model computed)"
                            % ", ".join(n for n in missing if self.kinds[n] == "ln_gamma"))
+        if self.conv and any(self.kinds[n] == "conv_kernel" for n in missing):
+            raise KeyError("checkpoint has no %s: a model with conv_layers = %d cannot start from a plain model's checkpoint "
+                           "(layer 0 reads the front-end's %d columns, not the %d input columns)"
+                           % (", ".join(n for n in missing if self.kinds[n] == "conv_kernel"), len(self.conv), self.D0, self.D))
+        if not self.conv and "conv0/kernel" in params:
+            raise KeyError("checkpoint has conv0/kernel: it was written by a model with conv_layers set, and this model (no "
+                           "conv_layers key) reads the input columns directly")
         if not self.layer_norm and "ln0/gamma" in params:
             raise KeyError("checkpoint has ln0/gamma: it was written by a model with layer_norm = true, and this model (no "
                            "layer_norm key) would compute something else with its other variables")
@@ -231,6 +249,10 @@ class ParamStore:
             if kind in ("lstm_kernel", "proj", "peephole"):
                 fan_in, fan_out = (shape[0], shape[1]) if len(shape) == 2 else (shape[0], shape[0])
                 lim = math.sqrt(6.0 / (fan_in + fan_out))
+                params[name] = rng.uniform(-lim, lim, size=shape).astype(np.float32)
+            elif kind == "conv_kernel":
+                # Glorot-uniform over the receptive field: fan_in = 9 Cin, fan_out = 9 Cout (the biases are zeros, below)
+                lim = math.sqrt(6.0 / (9 * shape[2] + 9 * shape[3]))
                 params[name] = rng.uniform(-lim, lim, size=shape).astype(np.float32)
             elif kind == "head_w":
                 if self.cudnn:
@@ -369,6 +391,74 @@ def layer_norm_info_line(cfg):
             "directions of a blstm layer together), dropout behind it; eps = %g" % (L - 1, ops.LN_EPS))
 
 
+CONV_MAX_LAYERS = 3
+
+
+def conv_config(cfg):
+    """The layers of the convolutional front-end (extension keys ``conv_layers`` / ``conv_channels`` / ``conv_bins``; DESIGN.md
+    3.20), validated: () when ``conv_layers`` is absent or 0 - today's model, and the other two keys are then not read -, else
+    one (Cin, Cout, F, Fo) per layer: layer k maps F_k bins to ceil(F_k / 2) bins and to ``conv_channels`` channels, the first
+    one reading ``input_dim / conv_bins`` channels of ``conv_bins`` bins.  Like the chunk keys it changes what the model
+    computes, so what cannot run it is refused here, by name."""
+    def integer(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        return int(v)
+    v = cfg.get("conv_layers")
+    if v is None:
+        return ()
+    n = integer("conv_layers", v)
+    if n < 0 or n > CONV_MAX_LAYERS:
+        raise ValueError("conv_layers must be in 0..%d (0: off), got %r" % (CONV_MAX_LAYERS, v))
+    if n == 0:
+        return ()
+    Cc = cfg.get("conv_channels")
+    Cc = 32 if Cc is None else integer("conv_channels", Cc)
+    if Cc < 8 or Cc > ops.CONV_MAX_CHANNELS or Cc % 8:
+        raise ValueError("conv_channels must be a multiple of 8 in 8..%d, got %r" % (ops.CONV_MAX_CHANNELS, Cc))
+    D = integer("input_dim", cfg.get("input_dim"))
+    F = cfg.get("conv_bins")
+    F = D if F is None else integer("conv_bins", F)
+    if F < 1 or F > ops.CONV_MAX_BINS or D % F:
+        raise ValueError("conv_bins must be in 1..%d and divide input_dim = %d, got %r" % (ops.CONV_MAX_BINS, D, F))
+    if D // F > ops.CONV_MAX_CHANNELS:
+        raise ValueError("conv_bins = %d leaves input_dim / conv_bins = %d input channels, more than %d"
+                         % (F, D // F, ops.CONV_MAX_CHANNELS))
+    if (cfg.get("left_context") or 0) or (cfg.get("right_context") or 0):
+        raise ValueError("conv_layers does not combine with left_context / right_context (%r, %r): the convolution supplies the "
+                         "context, and a spliced input has no frequency axis to convolve"
+                         % (cfg.get("left_context"), cfg.get("right_context")))
+    if cfg.get("use_bn"):
+        raise ValueError("conv_layers does not combine with use_bn: the batch normalisation of the input is not built in front "
+                         "of the convolution")
+    if cfg.get("pack_frames"):
+        raise ValueError("conv_layers does not combine with pack_frames = true: the convolution reads neighbouring frames of "
+                         "the padded layout")
+    cd = str(cfg.get("compute_dtype") or "fp32").lower()
+    if cd not in ("fp32", "float32", "f32"):
+        raise ValueError("conv_layers is built for compute_dtype = fp32 only, got compute_dtype = %s (the conv passes and the "
+                         "layer-0 dX they need are fp32)" % cd)
+    layers, Cin = [], D // F
+    for _ in range(n):
+        Fo = ops.conv_out_bins(F)
+        layers.append((Cin, Cc, F, Fo))
+        Cin, F = Cc, Fo
+    return tuple(layers)
+
+
+def conv_info_line(cfg):
+    """The INFO line of nnet-init / -train / -validate / -forward / -align when the key is on, else None."""
+    layers = conv_config(cfg)
+    if not layers:
+        return None
+    params = sum(9 * Cin * Cc + Cc for Cin, Cc, _, _ in layers)
+    return ("convolutional front-end: conv_layers = %d, conv_channels = %d, conv_bins = %d: %d input channels, bins %s, layer 0 "
+            "reads %d columns; %d parameters added; every logit reads %d more frames on each side"
+            % (len(layers), layers[0][1], layers[0][2], layers[0][0],
+               " -> ".join(str(f) for f in [layers[0][2]] + [l[3] for l in layers]), layers[-1][3] * layers[-1][1], params,
+               len(layers)))
+
+
 TIME_REDUCE_FACTORS = (2, 4)      # the library's range of r (lc_time_reduce_fwd)
 
 
@@ -438,7 +528,7 @@ def row_conv_identity(shape):
 def row_conv_horizon_raw(cfg):
     """(model frames, raw frames) the logits of a row-convolution model read past their own frame: tau, and that times the
     subsampling factor plus the splice's right context."""
-    tau = row_conv_config(cfg)
+    tau = row_conv_config(cfg) + len(conv_config(cfg))         # (the front-end reads one more model frame per layer)
     return tau, tau * max(int(cfg.get("subsample") or 0), 1) + int(cfg.get("right_context") or 0)
 
 
@@ -447,9 +537,9 @@ def row_conv_info_line(cfg):
     tau = row_conv_config(cfg)
     if not tau:
         return None
-    _, raw = row_conv_horizon_raw(cfg)
+    ahead, raw = row_conv_horizon_raw(cfg)
     return ("row convolution: row_conv_frames = %d: logits read %d model frames (%d raw frames) past their own"
-            % (tau, tau, raw))
+            % (tau, ahead, raw))
 
 
 def chunk_horizon(num_layers, Nc, Nr, c=0, T=None):
@@ -467,7 +557,7 @@ def chunk_horizon_raw(cfg):
     """(model frames, raw frames) a chunk's logits look past its end at worst, for the INFO line of the command-line tools:
     H_L(0) - Nc, and that times the subsampling factor plus the splice's right context."""
     Nc, Nr = chunk_config(cfg)
-    h = chunk_horizon(cfg["num_layers"], Nc, Nr) - Nc
+    h = chunk_horizon(cfg["num_layers"], Nc, Nr) - Nc + len(conv_config(cfg))    # (+ one model frame per front-end layer)
     return h, h * max(int(cfg.get("subsample") or 0), 1) + int(cfg.get("right_context") or 0)
 
 
@@ -506,6 +596,11 @@ class Model:
         # over its columns, with a gain and an offset ln{i}/gamma, ln{i}/beta, and the DropoutWrapper mask moves behind the
         # normalisation (lc_layer_norm_fwd / lc_layer_norm_bwd).  A plain checkpoint is refused by name.
         self.layer_norm = layer_norm_config(self.cfg)
+        # Extension keys conv_layers = n, conv_channels = Cc, conv_bins = F (absent or 0: off, the plain model to the bit): the
+        # convolutional front-end - n layers of 3 x 3 convolution over (time, frequency) with bias and ReLU, frequency stride 2,
+        # between x and layer 0, which reads the last one's [F_n * Cc] columns (lc_conv_fwd / lc_conv_bwd).
+        # Frame counts and lengths do not change.  fp32, no splice, no use_bn, no pack_frames: refused by name otherwise.
+        self.conv = conv_config(self.cfg)
         self.device = torch.device(device)
         self.ps = ParamStore(self.cfg, self.device)
         self.ps.init_random(seed)
@@ -575,6 +670,11 @@ class Model:
                 from . import tflog
                 tflog.info("pack_frames is built for compute_dtype = fp32 only; compute_dtype = %s runs on the padded rows" % cd)
             self.pack_frames = False
+        if self.pack_frames and self.conv:
+            # (LC_PACK_FRAMES=1 over a config without the key; the key itself is refused by conv_config)
+            from . import tflog
+            tflog.info("pack_frames does not combine with conv_layers; the model runs on the padded rows")
+            self.pack_frames = False
         if self.pack_frames and self.time_reduce:
             # (the frame map is built at one frame rate)
             global _PACK_REDUCE_LOGGED
@@ -589,12 +689,13 @@ class Model:
     def lookahead_horizon(self):
         """Latency-controlled mode: the worst-case number of model frames past a chunk's end that its logits read,
         H_L(0) - Nc (``chunk_horizon``); None when the mode is off (the whole utterance).  A row-convolution model
-        (unidirectional): tau, the model frames its logits read past their own."""
+        (unidirectional): tau, the model frames its logits read past their own.  Each layer of the convolutional front-end
+        adds one model frame to either."""
         if self.row_conv:
-            return self.row_conv
+            return self.row_conv + len(self.conv)
         if not self.chunk:
             return None
-        return chunk_horizon(self.ps.num_layers, self.chunk, self.lookahead) - self.chunk
+        return chunk_horizon(self.ps.num_layers, self.chunk, self.lookahead) - self.chunk + len(self.conv)
 
     def output_frames(self, T):
         """Frames of the logits for T input frames: T with ceil(. / r) applied once per reduced layer (= ceil(T / R))."""
@@ -766,6 +867,14 @@ class Model:
         self.packed = fm is not None and 0 < fm.M < rows
         pk_rows, pk_inverse = fm.device(dev) if self.packed else (None, None)
         inp = x.reshape(rows, D)
+        # the convolutional front-end: each layer's input and output are kept for its backward pass; the first layer reads the
+        # loader's layout (channels as blocks of F bins), the others what the layer below wrote.  D0: what layer 0 reads
+        conv_saved = []
+        for k, (_, _, F, _) in enumerate(self.conv):
+            y = ops.conv_fwd(inp, ps.p("conv%d/kernel" % k), ps.p("conv%d/bias" % k), seq_len, T, B, F, group_major=k == 0)
+            conv_saved.append(dict(x=inp, y=y, F=F, group_major=k == 0))
+            inp = y
+        D0 = ps.D0
         bn_saved = {}
         chunked = self.chunk > 0
         if chunked:
@@ -836,7 +945,7 @@ class Model:
             for dd in dirs:
                 if dd.get("hs_bf16") is not None:
                     self._adopt_shadow(dd["hs"], dd["hs_bf16"])
-            residual = (i == 0 and D == 2 * P) if ps.blstm else False               # bilstm.py:199
+            residual = (i == 0 and D0 == 2 * P) if ps.blstm else False              # bilstm.py:199
             # DropoutWrapper on each direction (layer_norm: Y stays unmasked, the mask goes on the normalised output below)
             drop = ps.blstm and self.keep < 1.0 and not ps.layer_norm
             # bf16 path: the pass that applies the mask also writes the bf16 shadow the next product reads
@@ -877,7 +986,7 @@ class Model:
             elif ps.cudnn:
                 residual = False                                                     # bare cells (lstm.py:73-76)
             else:
-                residual = not (i == 0 and D != P)                                   # lstm.py:236-260
+                residual = not (i == 0 and D0 != P)                                  # lstm.py:236-260
                 if residual:
                     ops.dropout_scale(inp, 1.0, 0, 0, out=Y, accumulate=True)        # ResidualWrapper
                     if ps.use_bn:         # a batch-normalised input is non-zero in the padded frames, but
@@ -908,7 +1017,7 @@ class Model:
             logits = self._mm(inp, ps.p("Variable"), bias=ps.p("Variable_1"))
         # (T and seq_len: the top layer's - what the head, the logits and encoder() are at; each layer keeps its own)
         self.saved = dict(layers=layers, head=head, T=T, B=B, seq_len=seq_len, drop_seed=drop_seed, bn=bn_saved,
-                          top=inp, pre_conv=pre_conv, frames=(pk_rows, pk_inverse) if self.packed else None,
+                          top=inp, pre_conv=pre_conv, conv=conv_saved, frames=(pk_rows, pk_inverse) if self.packed else None,
                           chunks=(Tc, Bc, len_c) if chunked else None)
         return logits.view(T, B, ps.V)
 
@@ -966,14 +1075,19 @@ class Model:
                                    ps.g(name + "/gamma"), ps.g(name + "/beta"), dx=d)
 
 
+        # a BiLSTM layer 0 as wide as the convolutional front-end's output adds it to its own (bilstm.py:199): the one case in
+        # which that residual carries a gradient - into the front-end
+        front_residual = bool(self.conv) and ps.blstm and sv["layers"][0]["residual"]
+
         def masked_dY(i, width, across_reduction=False):
             """The epilogue that finishes layer i's dY inside the product writing it (the DropoutWrapper's backward: the
             forward mask again, per direction), plus the bf16 shadow both products of each half (dh, dproj) read -
             or (None, None) when layer i masks in a pass of its own."""
             if (not (self.fuse_dropout and ps.blstm and self.keep < 1.0 and not ps.use_bn and not ps.layer_norm) or packed
-                    or across_reduction):
+                    or across_reduction or (i == 0 and front_residual)):
                 # (packed: the mask hashes the PADDED row index - it goes on the unpacked dY below; across a time reduction:
-                # it hashes the index at layer i's own frame rate - it goes on the un-reduced dY)
+                # it hashes the index at layer i's own frame rate - it goes on the un-reduced dY; layer 0 adding the
+                # front-end's output to its own: that residual branch takes the UNMASKED dY, so the mask goes on below)
                 return None, None
             d16 = (torch.empty((rows, width), dtype=torch.bfloat16, device=dl.device)
                    if self.bf16 and self.use_shadows and P % 4 == 0 else None)
@@ -1007,7 +1121,7 @@ class Model:
             T, seq_len = L["T"], L["seq_len"]
             rows = T * B
             ndir = len(cells)
-            need_dinp = i > 0 or ps.use_bn
+            need_dinp = i > 0 or ps.use_bn or bool(self.conv)
             dres = None
             if ps.use_bn:
                 dY = batch_norm_bwd("drnn_bn%d" % i, dY)
@@ -1016,6 +1130,9 @@ class Model:
                 ops.layer_norm_bwd(L["Y"], dY, ps.p("ln%d/gamma" % i), seq_len, T, B, self.keep, seed, 2 * i,
                                    P if ps.blstm else ndir * P, dx=dY, dgamma=ps.g("ln%d/gamma" % i),
                                    dbeta=ps.g("ln%d/beta" % i))
+            if ps.blstm and i == 0 and front_residual:
+                # Y_0 = dropout(concat) + front-end: its gradient is dY before the mask below (layer_norm: of the unmasked Y)
+                dres = dY.clone() if self.keep < 1.0 and not ps.layer_norm else dY
             if ps.blstm:
                 if premasked:                    # the product that wrote dY masked it and wrote its shadow
                     if dY16 is not None:
@@ -1215,6 +1332,14 @@ class Model:
                 dY, dY16, premasked = dinp, next16, ep is not None
         if ps.use_bn:
             batch_norm_bwd("drnn_bn_0_0", dY)
+        # the front-end, from its top layer down: dY is layer 0's dX (its dead frames are never read); the first layer has
+        # nobody to hand a dx to
+        L0 = sv["layers"][0]
+        for k in reversed(range(len(self.conv))):
+            c = sv["conv"][k]
+            dY, _, _ = ops.conv_bwd(c["x"], c["y"], dY, ps.p("conv%d/kernel" % k), L0["seq_len"], L0["T"], B, c["F"],
+                                    group_major=c["group_major"], want_dx=k > 0, dw=ps.g("conv%d/kernel" % k),
+                                    dbias=ps.g("conv%d/bias" % k))
         if keepalive:
             torch.cuda.current_stream().wait_stream(self._side)     # gradients complete before anyone reads them
             keepalive.clear()

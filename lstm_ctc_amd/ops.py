@@ -1109,6 +1109,92 @@ def layer_norm_bwd(x2d, dy2d, gamma, seq_len, T, B, keep=1.0, seed=0, stream0=0,
     return dx, dgamma, dbeta
 
 
+# ------------------------------------------------------------------------------------------ convolutional front-end
+CONV_MAX_CHANNELS, CONV_MAX_BINS = 64, 512      # the library's design caps (include/lstm_ctc_hip.h)
+# csrc/conv.hip's launch constants: the forward pass and the input gradient launch at most CONV_MAX_GROUPS workgroups, each on a
+# tile of CONV_FWD_FRAMES / CONV_DX_FRAMES frames of at most CONV_MAX_POS (utterance, bin) positions - more tiles than that and
+# a workgroup walks several; the weight gradient's CONV_DW_GROUPS workgroups split into ceil(Cin / 8) chunks of input channels
+# times the partials per weight, each walking tiles of CONV_DW_FRAMES frames x 16 output bins of one utterance
+CONV_MAX_GROUPS, CONV_FWD_FRAMES, CONV_DX_FRAMES, CONV_MAX_POS, CONV_DW_GROUPS, CONV_DW_FRAMES = 1024, 8, 4, 64, 1024, 8
+
+
+def conv_out_bins(F):
+    """Bins a conv layer writes for F input bins: ceil(F / 2) (kernel 3, stride 2, padding 1)."""
+    return (int(F) + 1) // 2
+
+
+def _conv_args(w, seq_len, T, B, F):
+    assert w.dim() == 4 and tuple(w.shape[:2]) == (3, 3) and w.dtype == torch.float32 and w.is_contiguous(), (w.shape, w.stride())
+    Cin, Cout = int(w.shape[2]), int(w.shape[3])
+    _check_lengths(seq_len, B)
+    if not (1 <= Cin <= CONV_MAX_CHANNELS and 8 <= Cout <= CONV_MAX_CHANNELS and Cout % 8 == 0 and 1 <= F <= CONV_MAX_BINS):
+        raise ValueError("conv: need Cin in 1..%d, Cout a multiple of 8 in 8..%d and F in 1..%d, got Cin %d, Cout %d, F %d"
+                         % (CONV_MAX_CHANNELS, CONV_MAX_CHANNELS, CONV_MAX_BINS, Cin, Cout, F))
+    return Cin, Cout, conv_out_bins(F)
+
+
+def conv_fwd(x2d, w, bias, seq_len, T, B, F, group_major=False, out=None):
+    """One layer of the convolutional front-end (lc_conv_fwd): x2d [T*B, Cin*F] time-major f32 (a 2-D view, last stride 1;
+    column ci * F + f with ``group_major``, else f * Cin + ci), w [3, 3, Cin, Cout] dense, bias [Cout], seq_len [B] int32 ->
+    out [T*B, ceil(F/2) * Cout] (column fo * Cout + co) = relu(conv2d(x, w, padding 1, stride (1, 2)) + bias) in live rows, +0
+    in dead ones.  Every element of out is written; dead rows of x are never read."""
+    lib = _lib.load()
+    _require_cuda(x2d, w, bias, seq_len, out)
+    T, B, F = int(T), int(B), int(F)
+    Cin, Cout, Fo = _conv_args(w, seq_len, T, B, F)
+    _check_rows(x2d, T * B, Cin * F)
+    assert bias.dtype == torch.float32 and tuple(bias.shape) == (Cout,) and bias.is_contiguous()
+    if out is None:
+        out = torch.empty((T * B, Fo * Cout), dtype=torch.float32, device=x2d.device)
+    _check_rows(out, T * B, Fo * Cout)
+    ev = _prof_begin()
+    _lib.check(lib.lc_conv_fwd(_ptr(x2d), _rows_pitch(x2d, Cin * F), int(bool(group_major)), _ptr(w), _ptr(bias), T, B, F, Cin,
+                               Cout, _ptr(seq_len), _ptr(out), _rows_pitch(out, Fo * Cout), _stream()), "lc_conv_fwd")
+    _prof_end("conv", 2.0 * 9 * Cin * Cout * Fo * T * B, ev)            # FLOPs
+    return out
+
+
+def conv_bwd(x2d, y2d, dy2d, w, seq_len, T, B, F, group_major=False, want_dx=True, want_dparams=True, dx=None, dw=None,
+             dbias=None):
+    """Gradients of conv_fwd (lc_conv_bwd) -> (dx [T*B, Cin*F] or None, dw [3, 3, Cin, Cout] or None, dbias [Cout] or None), with
+    g = dy2d where y2d > 0 (y2d: what conv_fwd wrote): dx the transposed convolution of g in live rows and +0 in dead ones, in
+    x2d's layout; dw = sum over the live positions of g * x, dbias = sum of g, both overwritten.  The workspace of the parameter
+    gradients is owned here."""
+    lib = _lib.load()
+    _require_cuda(x2d, y2d, dy2d, w, seq_len, dx, dw, dbias)
+    if not (want_dx or want_dparams):
+        raise ValueError("conv_bwd: want_dx and want_dparams are both false")
+    T, B, F = int(T), int(B), int(F)
+    Cin, Cout, Fo = _conv_args(w, seq_len, T, B, F)
+    _check_rows(y2d, T * B, Fo * Cout)
+    _check_rows(dy2d, T * B, Fo * Cout)
+    if want_dx:
+        if dx is None:
+            dx = torch.empty((T * B, Cin * F), dtype=torch.float32, device=dy2d.device)
+        _check_rows(dx, T * B, Cin * F)
+    else:
+        dx = None
+    ws, nbytes, xa = None, 0, None
+    if want_dparams:
+        xa = x2d
+        _check_rows(x2d, T * B, Cin * F)
+        dw = torch.empty((3, 3, Cin, Cout), dtype=torch.float32, device=dy2d.device) if dw is None else dw
+        dbias = torch.empty(Cout, dtype=torch.float32, device=dy2d.device) if dbias is None else dbias
+        assert dw.dtype == torch.float32 and tuple(dw.shape) == (3, 3, Cin, Cout) and dw.is_contiguous()
+        assert dbias.dtype == torch.float32 and tuple(dbias.shape) == (Cout,) and dbias.is_contiguous()
+        nbytes = lib.lc_conv_workspace_bytes(T, B, F, Cin, Cout)
+        ws = workspace("conv", nbytes, dy2d.device)
+    else:
+        dw = dbias = None
+    ev = _prof_begin()
+    _lib.check(lib.lc_conv_bwd(_ptr(xa), _rows_pitch(xa, Cin * F) if xa is not None else Cin * F, int(bool(group_major)),
+                               _ptr(y2d), _rows_pitch(y2d, Fo * Cout), _ptr(dy2d), _rows_pitch(dy2d, Fo * Cout), _ptr(w), T, B, F,
+                               Cin, Cout, _ptr(seq_len), _ptr(dx), _rows_pitch(dx, Cin * F) if dx is not None else Cin * F,
+                               _ptr(dw), _ptr(dbias), _ptr(ws), nbytes, _stream()), "lc_conv_bwd")
+    _prof_end("conv", 2.0 * 9 * Cin * Cout * Fo * T * B * (bool(want_dx) + bool(want_dparams)), ev)
+    return dx, dw, dbias
+
+
 # ------------------------------------------------------------------------------------------ SpecAugment
 def _tbd_pitch(t, T, B, D):
     """Row pitch of a time-major [T, B, D] tensor whose T * B rows lie at one pitch (a column window of a wider buffer is
